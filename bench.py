@@ -3,6 +3,21 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--arch resnet50] [--batch 256]
                     [--impl native|torch] [--bucket-mb 25] [--wire-dtype fp32|bf16]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds
+the untimed extras after the timed region: the host issue cost of a step on an idle device
+(``host_issue_ms``; with ``PDT_HOST_PROFILE`` / ``PDT_DIAG_LEAD`` their diagnostics), the
+all-gathered parameter checksum (``ranks_identical``, ``param_checksum``) and one extra step's
+all-reduce time / exposed tail (``comm_ms``, ``exposed_ms``).  ``--dump-outputs DIR`` writes what
+the last timed step computed (logits, loss, updated parameters) as ``DIR/<name>.npy``, with the
+kernels the other arguments select.  The default kernels reduce with fp32 atomics, whose order
+differs from run to run, and training amplifies that rounding step by step (logits 5 % apart after
+60 ResNet-50 steps).  So with the option, the weights and the momentum are put back to their seeded
+initial values just before the last timed step (one copy inside the timed region, ~0.2 ms): the
+dumped step follows no drifted history, and two runs differ by one step's rounding only (logits
+and loss equal, parameters ~4e-5 relative L2); with ``--deterministic`` they are bit-identical.
+``--fp8`` keeps its delayed-scaling history, so its dump still follows the earlier steps.
 
 For N > 1 it is launched one process per GPU by torchrun (RANK/LOCAL_RANK/
 WORLD_SIZE/MASTER_* from the env); if started without torchrun and --gpus > 1
@@ -91,7 +106,19 @@ def parse(argv=None):
                         "minCTAs/maxCTAs; default: RCCL's choice)")
     p.add_argument("--cudnn-benchmark", action="store_true",
                    help="stock path: let MIOpen search for the fastest conv solutions")
-    return p.parse_args(argv)
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed (rank 0: logits, "
+                        "loss, updated parameters) as DIR/<name>.npy in float32; that step starts from the "
+                        "seeded initial weights and zero momentum again, so two runs differ by one step's "
+                        "rounding only (bit-identical with --deterministic)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the untimed extras after the timed region: host issue cost on an idle "
+                        "device (and the PDT_HOST_PROFILE / PDT_DIAG_LEAD diagnostics), the all-gathered "
+                        "parameter checksum, one extra step's all-reduce time / exposed tail")
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _relaunch_with_torchrun(args_argv, n) -> int:
@@ -131,6 +158,63 @@ def _param_checksums(ddp, impl, world, dev):
     return all(v == vals[0] for v in vals), vals[0]
 
 
+DUMP_MAX_ELEMS = 8 * 2**20  # per array (32 MiB of float32): larger outputs are sampled
+
+
+def _dump_outputs(path, out, loss, ddp, impl) -> None:
+    """--dump-outputs: what the last timed step handed its caller, as float32 ``.npy`` files --
+    ``logits`` (the model output; not with --graph), ``loss``, and ``params`` (every parameter
+    after the update, flattened in order; when longer than DUMP_MAX_ELEMS, a fixed seeded sample
+    of its elements)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    with torch.no_grad():
+        if impl == "native":
+            flat = ddp.space.param_flat.detach().reshape(-1)
+        else:
+            flat = torch.cat([p.detach().reshape(-1) for p in ddp.parameters()])
+        if flat.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(4321)
+            idx = torch.randperm(flat.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values  # distinct
+            flat = flat[idx.to(flat.device)]
+        arrays = {"loss": loss.detach().reshape(1), "params": flat}
+        if out is not None:
+            arrays["logits"] = out.detach()
+        for name, t in arrays.items():
+            np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
+def _make_rewind(ddp, opt, impl):
+    """--dump-outputs: snapshot the (seeded) initial parameters now; the returned function puts
+    them back and zeroes the momentum (an update from zero momentum equals the first update, which
+    initialises the buffer with the gradient), so the step after it computes what the run's first
+    step computed.  BatchNorm running statistics do not enter a training step's outputs and stay."""
+    import torch
+    with torch.no_grad():
+        if impl == "native":
+            space = ddp.space
+            snap = space.param_flat.detach().clone()
+        else:
+            params = list(ddp.parameters())
+            snap = [p.detach().clone() for p in params]
+
+    def rewind():
+        with torch.no_grad():
+            if impl == "native":
+                space.param_flat.copy_(snap)
+                mirror = space.mirror()
+                if mirror is not None:
+                    mirror.refresh()  # the bf16 weight images follow the parameters
+            else:
+                torch._foreach_copy_(params, snap)
+            flat_bufs = list(getattr(opt, "_flat_bufs", {}).values())  # fused SGD: one buffer
+            for buf in flat_bufs or [st["momentum_buffer"] for st in opt.state.values()
+                                     if st.get("momentum_buffer") is not None]:
+                buf.zero_()
+    return rewind
+
+
 def _last_mb(v: str):
     if v in ("auto", "none"):
         return None if v == "none" else v
@@ -167,6 +251,42 @@ def _diag_lead(step, barrier, dev, nsteps: int = 8) -> None:
     a = starts[-1]
     for tag, h, g in rows[a:]:
         print(f"[lead]   {tag:28s} host {h:8.2f} device {g:8.2f} lead {g - h:6.2f} ms", flush=True)
+
+
+def _host_issue_ms(step, barrier, rank) -> float:
+    """--full: host issue cost of one step from an idle device (untimed, after the timed region):
+    the time inside step() in the timed loop also counts waits on a full launch queue whenever the
+    GPU is the bound.  PDT_HOST_PROFILE=<file>: cProfile of these idle-device steps (diagnostic)."""
+    import torch
+    issue = []
+    prof_path = os.environ.get("PDT_HOST_PROFILE")
+    prof = None
+    if prof_path and rank == 0:
+        import cProfile
+        prof = cProfile.Profile()
+    for _ in range(3):
+        barrier()
+        th = time.perf_counter()
+        if prof is not None:
+            # backward on this thread, so cProfile sees the autograd Functions' Python too
+            with torch.autograd.set_multithreading_enabled(False):
+                prof.enable()
+                step()
+                prof.disable()
+        else:
+            step()
+        issue.append(time.perf_counter() - th)
+    barrier()
+    if prof is not None:
+        import io
+        import pstats
+        buf = io.StringIO()
+        st_ = pstats.Stats(prof, stream=buf)
+        st_.sort_stats("tottime").print_stats(60)
+        st_.sort_stats("cumulative").print_stats(60)
+        with open(prof_path, "w") as f:
+            f.write(buf.getvalue())
+    return 1000.0 * min(issue)
 
 
 def main(argv=None) -> int:
@@ -265,6 +385,11 @@ def main(argv=None) -> int:
     if os.environ.get("PDT_DIAG_BLOCKED") == "1" and dev.type == "cuda":
         diag_blocked = (torch.cuda.Stream(), torch.zeros(16, device=dev))
 
+    # --dump-outputs: the last step's logits (a replayed graph hands its caller the loss only)
+    kept = {} if args.dump_outputs and not args.graph else None
+    # ... and that step starts from the seeded initial weights again (see the module docstring)
+    rewind = _make_rewind(ddp, opt, args.impl) if args.dump_outputs else None
+
     def step():
         opt.zero_grad()
         if autocast is not None:
@@ -274,6 +399,8 @@ def main(argv=None) -> int:
         else:
             out = ddp(images)
             loss = criterion(out, labels)
+        if kept is not None:
+            kept["logits"] = out.detach()
         if diag_blocked is not None:  # PDT_DIAG_BLOCKED: a side queue parked on a barrier
             ev = torch.cuda.Event()
             ev.record()
@@ -311,6 +438,8 @@ def main(argv=None) -> int:
     host = 0.0  # host time spent inside step() (issue time; ~= step time when the host is the bound)
     for i in range(args.steps):
         beat(f"step {i}")
+        if rewind is not None and i == args.steps - 1:
+            rewind()
         th = time.perf_counter()
         loss = step()
         host += time.perf_counter() - th
@@ -321,53 +450,28 @@ def main(argv=None) -> int:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     final_loss = float(loss.item())
-    # host issue cost of one step from an idle device (untimed, after the timed region): the time
-    # inside step() above also counts waits on a full launch queue whenever the GPU is the bound
-    issue = []
-    prof_path = os.environ.get("PDT_HOST_PROFILE")  # cProfile of these idle-device steps (diagnostic)
-    prof = None
-    if prof_path and env.rank == 0:
-        import cProfile
-        prof = cProfile.Profile()
-    for _ in range(3):
-        barrier()
-        th = time.perf_counter()
-        if prof is not None:
-            # backward on this thread, so cProfile sees the autograd Functions' Python too
-            with torch.autograd.set_multithreading_enabled(False):
-                prof.enable()
-                step()
-                prof.disable()
-        else:
-            step()
-        issue.append(time.perf_counter() - th)
-    barrier()
-    if prof is not None:
-        import io
-        import pstats
-        buf = io.StringIO()
-        st_ = pstats.Stats(prof, stream=buf)
-        st_.sort_stats("tottime").print_stats(60)
-        st_.sort_stats("cumulative").print_stats(60)
-        with open(prof_path, "w") as f:
-            f.write(buf.getvalue())
-    host_issue_ms = 1000.0 * min(issue)
-    if os.environ.get("PDT_DIAG_LEAD") == "1" and dev.type == "cuda" and args.impl == "native":
-        _diag_lead(step, barrier, dev)
-    # every rank must hold bit-identical parameters after the run (untimed): a positional int64
-    # checksum of the parameter bits, all-gathered -- a fast-but-wrong multi-GPU run shows here
-    ranks_identical, param_checksum = _param_checksums(ddp, args.impl, world, dev)
+    if args.dump_outputs and env.rank == 0:
+        _dump_outputs(args.dump_outputs, kept["logits"] if kept else None, loss, ddp, args.impl)
+    host_issue_ms = ranks_identical = param_checksum = None
+    if args.full:
+        host_issue_ms = _host_issue_ms(step, barrier, env.rank)
+        if os.environ.get("PDT_DIAG_LEAD") == "1" and dev.type == "cuda" and args.impl == "native":
+            _diag_lead(step, barrier, dev)
+        # every rank must hold bit-identical parameters after the run (untimed): a positional int64
+        # checksum of the parameter bits, all-gathered -- a fast-but-wrong multi-GPU run shows here
+        ranks_identical, param_checksum = _param_checksums(ddp, args.impl, world, dev)
     comm = None
     if args.impl == "native":
         info = ddp.bucket_info()
         comm = {"native_comm": info["native_comm"], "reducer": info["reducer"], "xgmi": info["xgmi"], "wgrad_cu_reserve": info.get("wgrad_cu_reserve", 0),
                 "buckets_mb": [round(b / 2**20, 2) for b in info["bucket_bytes"]]}
         # diagnostics for the scaling run (untimed, after the timed region): what the communicator
-        # reports about itself, and one step's all-reduce time / exposed tail from the reducer's
-        # HIP events (time from the first bucket's launch to the last bucket's end on the comm
-        # stream; exposed = the part after the backward's last kernel)
+        # reports about itself, and (--full, or the timed steps' last with --comm-timing) one
+        # step's all-reduce time / exposed tail from the reducer's HIP events (time from the first
+        # bucket's launch to the last bucket's end on the comm stream; exposed = the part after
+        # the backward's last kernel)
         comm.update(ddp.comm_diagnostics())
-        if not args.comm_timing and not args.graph and ddp.enable_comm_timing(True):
+        if args.full and not args.comm_timing and not args.graph and ddp.enable_comm_timing(True):
             step()
             barrier()
         st = ddp.comm_stats()
@@ -393,7 +497,8 @@ def main(argv=None) -> int:
             "warmup": args.warmup,
             "ms_per_step": round(1000.0 * elapsed / args.steps, 3),
             "host_ms_per_step": round(1000.0 * host / args.steps, 3),
-            "host_issue_ms": round(host_issue_ms, 3),
+            "host_issue_ms": round(host_issue_ms, 3) if host_issue_ms is not None else None,
+            "full": bool(args.full),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": (round(img_s / base, 4) if base else None),

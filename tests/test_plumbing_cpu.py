@@ -235,7 +235,8 @@ def test_bench_two_ranks_gloo(tmp_path):
     out = tmp_path / "b.json"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--arch", "resnet18",
                         "--image-size", "32", "--num-classes", "10", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--impl", "torch", "--backend", "gloo", "--json-out", str(out)],
+                        "--warmup", "1", "--impl", "torch", "--backend", "gloo", "--full",
+                        "--json-out", str(out)],
                        cwd=root, env=env, timeout=300, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -263,7 +264,7 @@ def test_bench_two_ranks_native_reports_comm_diagnostics(tmp_path):
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--arch", "resnet18",
                         "--image-size", "32", "--num-classes", "10", "--batch", "4", "--steps", "2",
-                        "--warmup", "1", "--impl", "native", "--backend", "gloo"],
+                        "--warmup", "1", "--impl", "native", "--backend", "gloo", "--full"],
                        cwd=root, env=env, timeout=300, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -275,6 +276,47 @@ def test_bench_two_ranks_native_reports_comm_diagnostics(tmp_path):
     assert c["backend"] == "python-gloo" and c["wire_dtype"] == "fp32"
     assert len(c["buckets_mb"]) >= 2 and all(b > 0 for b in c["buckets_mb"])
     assert "WARNING" not in r.stdout
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain ``bench.py`` run times exactly ``--steps`` steps and skips the ``--full`` extras;
+    ``--dump-outputs`` writes the last timed step's logits / loss / parameters as float32 ``.npy``,
+    computed from the seeded initial weights (put back before that step): a run of 1 + 3 steps
+    dumps exactly what a run of one single step from the same seed dumps (the CPU ops are
+    deterministic), and the run does not switch to the deterministic kernels on its own."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run, steps, warmup in (("a", 3, 1), ("b", 1, 0)):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--arch", "resnet18",
+                            "--image-size", "32", "--num-classes", "10", "--batch", "4", "--steps", str(steps),
+                            "--warmup", str(warmup), "--impl", "native", "--dump-outputs", str(d)],
+                           cwd=root, env=env, timeout=300, capture_output=True, text=True)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == steps and res["warmup"] == warmup and res["ms_per_step"] > 0
+        assert abs(res["value"] - 4 / (res["ms_per_step"] / 1000.0)) / res["value"] < 1e-2
+        assert res["full"] is False and res["host_issue_ms"] is None
+        assert res["config"]["deterministic"] is False
+        assert res["config"]["ranks_identical"] is None and res["config"]["param_checksum"] is None
+        assert sorted(os.listdir(d)) == ["logits.npy", "loss.npy", "params.npy"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("logits", "loss", "params")})
+    a, b = dumps
+    assert a["logits"].shape == (4, 10) and a["loss"].shape == (1,) and a["params"].ndim == 1
+    assert abs(float(a["loss"][0]) - res["config"]["final_loss"]) < 1e-3
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all()
+        assert np.array_equal(a[n], b[n]), n
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
 
 
 def test_bn_counter_list_cache_follows_mode_and_surgery():

@@ -333,7 +333,8 @@ def test_bench_force_comm_reports_diagnostics(gpu, tmp_path):
     import json
     out = tmp_path / "b.json"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--arch", "resnet18", "--image-size", "64",
-                        "--batch", "32", "--steps", "2", "--warmup", "1", "--force-comm", "--json-out", str(out)],
+                        "--batch", "32", "--steps", "2", "--warmup", "1", "--force-comm", "--full",
+                        "--json-out", str(out)],
                        cwd=ROOT, timeout=300, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     cfg = json.loads(out.read_text())["config"]
