@@ -1247,8 +1247,9 @@ std::tuple<Tensor, Tensor, Tensor> fc_backward(const Tensor& dlogits, const Tens
 }
 
 // -------------------------------------------------------------------- head
-std::tuple<Tensor, Tensor> softmax_xent(const Tensor& logits_in, const Tensor& labels) {
+std::tuple<Tensor, Tensor> softmax_xent(const Tensor& logits_in, const Tensor& labels, double label_smoothing) {
   check_cuda(logits_in, "logits");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0, "label_smoothing must be in [0, 1]");
   c10::hip::HIPGuard g(logits_in.get_device());
   Tensor logits = logits_in.scalar_type() == at::kFloat ? logits_in : logits_in.to(at::kFloat);
   TORCH_CHECK(labels.scalar_type() == at::kLong, "labels must be int64");
@@ -1257,7 +1258,8 @@ std::tuple<Tensor, Tensor> softmax_xent(const Tensor& logits_in, const Tensor& l
   auto dl = at::empty_like(logits);
   auto ws = at::empty({N}, logits.options());
   pdt::launch_softmax_xent(logits.data_ptr<float>(), labels.data_ptr<int64_t>(), loss.data_ptr<float>(),
-                           dl.data_ptr<float>(), ws.data_ptr<float>(), N, V, cur_stream(logits));
+                           dl.data_ptr<float>(), ws.data_ptr<float>(), N, V, cur_stream(logits),
+                           (float)label_smoothing);
   return {loss, dl};
 }
 
@@ -1321,6 +1323,136 @@ void sgd_step(Tensor p, const Tensor& g, const std::optional<Tensor>& buf_opt, d
                   p.numel(), (float)lr, (float)momentum, (float)dampening, (float)wd, nesterov, first,
                   (float)grad_scale, cur_stream(p), pb);
 }
+
+// -------------------------------------------------------------------- lars
+// table: device bytes, trust.numel() segment entries then partials.numel()/2 chunk entries
+// (optim/lars.py builds it); partials: float64 [nchunks][2]; trust: fp32 [nseg]
+pdt::LarsSpace lars_space(const Tensor& table, const Tensor& partials, const Tensor& trust, int64_t numel,
+                          int64_t seg_lo, int64_t seg_hi) {
+  check_cuda(table, "table");
+  check_cuda(partials, "partials");
+  check_cuda(trust, "trust");
+  TORCH_CHECK(table.scalar_type() == at::kByte, "lars: table must be a device byte tensor");
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials.numel() % 2 == 0,
+              "lars: partials must be float64 [nchunks][2]");
+  TORCH_CHECK(trust.scalar_type() == at::kFloat && trust.numel() > 0, "lars: trust must be fp32 [nseg]");
+  const int64_t nseg = trust.numel(), nchunks = partials.numel() / 2;
+  TORCH_CHECK(nseg < (int64_t(1) << 30) && nchunks < (int64_t(1) << 30), "lars: table too large");
+  TORCH_CHECK(table.numel() == nseg * (int64_t)pdt::lars_entry_bytes() +
+                                   nchunks * (int64_t)pdt::lars_chunk_entry_bytes(),
+              "lars: table size does not match trust (segments) and partials (chunks)");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(table.data_ptr()) & 15) == 0 &&
+              (reinterpret_cast<uintptr_t>(partials.data_ptr()) & 7) == 0, "lars: table alignment");
+  TORCH_CHECK(0 <= seg_lo && seg_lo <= seg_hi && seg_hi <= nseg, "lars: segment range [", seg_lo, ", ", seg_hi,
+              ") outside [0, ", nseg, ")");
+  pdt::LarsSpace sp;
+  sp.table = table.data_ptr();
+  sp.nseg = (int)nseg;
+  sp.nchunks = (int)nchunks;
+  sp.numel = numel;
+  sp.partials = partials.data_ptr<double>();
+  sp.trust = trust.data_ptr<float>();
+  return sp;
+}
+
+void lars_trust(const Tensor& p, const Tensor& g, const Tensor& table, Tensor partials, Tensor trust,
+                int64_t seg_lo, int64_t seg_hi, double wd, double eta, double eps) {
+  check_cuda(p, "param");
+  check_cuda(g, "grad");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "fp32 flat buffers only");
+  TORCH_CHECK(p.numel() == g.numel(), "param/grad size mismatch");
+  pdt::LarsSpace sp = lars_space(table, partials, trust, p.numel(), seg_lo, seg_hi);
+  c10::hip::HIPGuard gd(p.get_device());
+  hipStream_t st = cur_stream(p);
+  pdt::launch_lars_norms(p.data_ptr<float>(), g.data_ptr<float>(), sp, (int)seg_lo, (int)seg_hi, sp.nchunks, st);
+  pdt::launch_lars_trust(sp, (int)seg_lo, (int)seg_hi, wd, eta, eps, st);
+}
+
+// the passes of lars_trust one at a time (per-pass timing)
+void lars_norms(const Tensor& p, const Tensor& g, const Tensor& table, Tensor partials, Tensor trust,
+                int64_t seg_lo, int64_t seg_hi) {
+  check_cuda(p, "param");
+  check_cuda(g, "grad");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && p.numel() == g.numel(),
+              "fp32 flat buffers of one size only");
+  pdt::LarsSpace sp = lars_space(table, partials, trust, p.numel(), seg_lo, seg_hi);
+  c10::hip::HIPGuard gd(p.get_device());
+  pdt::launch_lars_norms(p.data_ptr<float>(), g.data_ptr<float>(), sp, (int)seg_lo, (int)seg_hi, sp.nchunks,
+                         cur_stream(p));
+}
+
+void lars_trust_only(const Tensor& table, Tensor partials, Tensor trust, int64_t seg_lo, int64_t seg_hi,
+                     double wd, double eta, double eps) {
+  pdt::LarsSpace sp = lars_space(table, partials, trust, 0, seg_lo, seg_hi);
+  c10::hip::HIPGuard gd(trust.get_device());
+  pdt::launch_lars_trust(sp, (int)seg_lo, (int)seg_hi, wd, eta, eps, cur_stream(trust));
+}
+
+void lars_step(Tensor p, const Tensor& g, const std::optional<Tensor>& buf_opt, const Tensor& table,
+               Tensor partials, Tensor trust, int64_t seg_lo, int64_t seg_hi, double lr, double momentum,
+               double dampening, double wd, bool nesterov, bool first, double eta, double eps,
+               const std::optional<Tensor>& p_bf16) {
+  check_cuda(p, "param");
+  check_cuda(g, "grad");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat, "fp32 flat buffers only");
+  TORCH_CHECK(p.numel() == g.numel(), "param/grad size mismatch");
+  bool mom = momentum != 0.0;
+  Tensor buf = buf_opt.has_value() ? *buf_opt : Tensor();  // momentum 0: no buffer (None)
+  if (mom) {
+    TORCH_CHECK(buf.defined(), "lars_step: momentum != 0 needs a momentum buffer");
+    check_cuda(buf, "momentum_buffer");
+    TORCH_CHECK(buf.scalar_type() == at::kFloat && buf.numel() == p.numel(), "momentum buffer size mismatch");
+  }
+  auto aligned = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  TORCH_CHECK(aligned(p.data_ptr()) && aligned(g.data_ptr()) && (!mom || aligned(buf.data_ptr())),
+              "lars_step: flat buffers must be 16-byte aligned");
+  uint16_t* pb = nullptr;
+  if (p_bf16.has_value() && p_bf16->defined()) {
+    check_cuda(*p_bf16, "p_bf16");
+    TORCH_CHECK(p_bf16->scalar_type() == at::kBFloat16 && p_bf16->numel() == p.numel(),
+                "lars_step: bf16 mirror must match the parameter buffer");
+    TORCH_CHECK(aligned(p_bf16->data_ptr()), "mirror must be 16-B aligned");
+    pb = bf(*p_bf16);
+  }
+  pdt::LarsSpace sp = lars_space(table, partials, trust, p.numel(), seg_lo, seg_hi);
+  c10::hip::HIPGuard gd(p.get_device());
+  pdt::launch_lars(p.data_ptr<float>(), g.data_ptr<float>(), mom ? buf.data_ptr<float>() : nullptr, sp,
+                   (int)seg_lo, (int)seg_hi, sp.nchunks, (float)lr, (float)momentum, (float)dampening, wd,
+                   nesterov, first, eta, eps, cur_stream(p), pb);
+}
+
+// the update pass alone, with the trust ratios already in `trust` (diagnostics / per-pass timing)
+void lars_update(Tensor p, const Tensor& g, const std::optional<Tensor>& buf_opt, const Tensor& table,
+                 Tensor partials, Tensor trust, int64_t seg_lo, int64_t seg_hi, double lr, double momentum,
+                 double dampening, double wd, bool nesterov, bool first, const std::optional<Tensor>& p_bf16) {
+  check_cuda(p, "param");
+  check_cuda(g, "grad");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && g.scalar_type() == at::kFloat && p.numel() == g.numel(),
+              "fp32 flat buffers of one size only");
+  bool mom = momentum != 0.0;
+  Tensor buf = buf_opt.has_value() ? *buf_opt : Tensor();
+  if (mom) {
+    TORCH_CHECK(buf.defined(), "lars_update: momentum != 0 needs a momentum buffer");
+    check_cuda(buf, "momentum_buffer");
+    TORCH_CHECK(buf.scalar_type() == at::kFloat && buf.numel() == p.numel(), "momentum buffer size mismatch");
+  }
+  uint16_t* pb = nullptr;
+  if (p_bf16.has_value() && p_bf16->defined()) {
+    check_cuda(*p_bf16, "p_bf16");
+    TORCH_CHECK(p_bf16->scalar_type() == at::kBFloat16 && p_bf16->numel() == p.numel(),
+                "lars_update: bf16 mirror must match the parameter buffer");
+    pb = bf(*p_bf16);
+  }
+  pdt::LarsSpace sp = lars_space(table, partials, trust, p.numel(), seg_lo, seg_hi);
+  c10::hip::HIPGuard gd(p.get_device());
+  pdt::launch_lars_update(p.data_ptr<float>(), g.data_ptr<float>(), mom ? buf.data_ptr<float>() : nullptr, sp,
+                          (int)seg_lo, (int)seg_hi, sp.nchunks, (float)lr, (float)momentum, (float)dampening,
+                          (float)wd, nesterov, first, cur_stream(p), pb);
+}
+
+int64_t lars_entry_bytes() { return (int64_t)pdt::lars_entry_bytes(); }
+int64_t lars_chunk_entry_bytes() { return (int64_t)pdt::lars_chunk_entry_bytes(); }
+int64_t lars_chunk_elems() { return (int64_t)pdt::lars_chunk_elems(); }
 
 // flat fp32 -> bf16 mirror (refresh when parameters changed outside the fused SGD step)
 void cast_to_bf16(const Tensor& x, Tensor y) {
@@ -1550,11 +1682,31 @@ PYBIND11_MODULE(_C, m) {
         py::arg("weight"), py::arg("dw_out") = py::none(), py::arg("db_out") = py::none());
   m.def("scale_by", checked("scale_by", &scale_by), py::arg("x"), py::arg("alpha"));
   m.def("add_one_i64", checked("add_one_i64", &add_one_i64), py::arg("x"));
-  m.def("softmax_xent", checked("softmax_xent", &softmax_xent));
+  m.def("softmax_xent", checked("softmax_xent", &softmax_xent), py::arg("logits"), py::arg("labels"),
+        py::arg("label_smoothing") = 0.0);
   m.def("top1_correct", checked("top1_correct", &top1_correct));
   m.def("sgd_step", checked("sgd_step", &sgd_step), py::arg("p"), py::arg("g"), py::arg("buf"),
         py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("wd"), py::arg("nesterov"),
         py::arg("first"), py::arg("grad_scale"), py::arg("p_bf16") = py::none());
+  m.def("lars_step", checked("lars_step", &lars_step), py::arg("p"), py::arg("g"), py::arg("buf"),
+        py::arg("table"), py::arg("partials"), py::arg("trust"), py::arg("seg_lo"), py::arg("seg_hi"),
+        py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("first"), py::arg("eta"), py::arg("eps"), py::arg("p_bf16") = py::none());
+  m.def("lars_trust", checked("lars_trust", &lars_trust), py::arg("p"), py::arg("g"), py::arg("table"),
+        py::arg("partials"), py::arg("trust"), py::arg("seg_lo"), py::arg("seg_hi"), py::arg("weight_decay"),
+        py::arg("eta"), py::arg("eps"));
+  m.def("lars_update", checked("lars_update", &lars_update), py::arg("p"), py::arg("g"), py::arg("buf"),
+        py::arg("table"), py::arg("partials"), py::arg("trust"), py::arg("seg_lo"), py::arg("seg_hi"),
+        py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"),
+        py::arg("first"), py::arg("p_bf16") = py::none());
+  m.def("lars_norms", checked("lars_norms", &lars_norms), py::arg("p"), py::arg("g"), py::arg("table"),
+        py::arg("partials"), py::arg("trust"), py::arg("seg_lo"), py::arg("seg_hi"));
+  m.def("lars_trust_only", checked("lars_trust_only", &lars_trust_only), py::arg("table"), py::arg("partials"),
+        py::arg("trust"), py::arg("seg_lo"), py::arg("seg_hi"), py::arg("weight_decay"), py::arg("eta"),
+        py::arg("eps"));
+  m.def("lars_entry_bytes", &lars_entry_bytes);
+  m.def("lars_chunk_entry_bytes", &lars_chunk_entry_bytes);
+  m.def("lars_chunk_elems", &lars_chunk_elems);
   m.def("cast_to_bf16", checked("cast_to_bf16", &cast_to_bf16));
   m.def("pack_t_batched", checked("pack_t_batched", &pack_t_batched));
   m.def("pack_t_entry_bytes", &pack_t_entry_bytes);
@@ -1743,6 +1895,8 @@ PYBIND11_MODULE(_C, m) {
            }, py::arg("lr"), py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"),
            py::arg("nesterov"), py::arg("first"), py::arg("momentum_buf") = py::none(),
            py::arg("mirror") = py::none())
+      .def("arm_lars", &pdt::Reducer::arm_lars, py::arg("table"), py::arg("partials"), py::arg("trust"),
+           py::arg("weight_decay"), py::arg("eta"), py::arg("eps"), py::arg("bucket_ranges"))
       .def("optimizer_applied", &pdt::Reducer::optimizer_applied)
       .def("consume_optimizer", &pdt::Reducer::consume_optimizer)
       .def_property_readonly("local", &pdt::Reducer::local);

@@ -10,6 +10,7 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <array>
 #include <cstdlib>
 #include <stdexcept>
 
@@ -70,6 +71,13 @@ struct ReducerState {
   uint16_t* sgd_pb = nullptr;
   int64_t sgd_applied = 0;
   std::pair<int64_t, int64_t> sgd_last{-1, -1};
+  // optional LARS block (arm_lars after arm_optimizer): the per-bucket update then is the LARS
+  // passes over the bucket's segment range instead of the plain fused SGD
+  bool lars_on = false;
+  LarsSpace lars{};
+  at::Tensor lars_table, lars_partials, lars_trust;  // keep the device buffers alive while armed
+  double lars_wd = 0.0, lars_eta = 0.0, lars_eps = 0.0;
+  std::vector<std::array<int, 3>> lars_ranges;  // per bucket: seg_lo, seg_hi, chunks in that range
 
   std::mutex mu;
   bool enabled = true;
@@ -94,6 +102,13 @@ struct ReducerState {
   // the fused SGD over bucket b's flat range, on stream s behind its reduction
   void apply_sgd(int64_t b, hipStream_t s) {
     if (!sgd_armed) return;
+    if (lars_on) {
+      const auto& r = lars_ranges[b];
+      launch_lars(sgd_p, grad_base, sgd_buf, lars, r[0], r[1], r[2], sgd_lr, sgd_mom, sgd_damp, lars_wd,
+                  sgd_nest, sgd_first, lars_eta, lars_eps, s, sgd_pb);
+      ++sgd_applied;
+      return;
+    }
     const int64_t off = goff[b];
     launch_sgd(sgd_p + off, grad_base + off, sgd_buf ? sgd_buf + off : nullptr, flats[b].numel(), sgd_lr,
                sgd_mom, sgd_damp, sgd_wd, sgd_nest, sgd_first, 1.f, s, sgd_pb ? sgd_pb + off : nullptr);
@@ -454,6 +469,51 @@ void Reducer::arm_optimizer(double lr, double momentum, double dampening, double
   st_->sgd_applied = 0;
   st_->sgd_armed = true;
   st_->sgd_last = {-1, -1};
+  st_->lars_on = false;
+}
+
+void Reducer::arm_lars(const at::Tensor& table, const at::Tensor& partials, const at::Tensor& trust,
+                       double weight_decay, double eta, double eps,
+                       const std::vector<std::array<int64_t, 3>>& bucket_ranges) {
+  std::lock_guard<std::mutex> lk(st_->mu);
+  if (!st_->sgd_armed) throw std::runtime_error("Reducer::arm_lars needs arm_optimizer first");
+  auto dev = [](const at::Tensor& t) { return t.defined() && t.is_cuda() && t.is_contiguous(); };
+  if (!dev(table) || !dev(partials) || !dev(trust) || table.scalar_type() != at::kByte ||
+      partials.scalar_type() != at::kDouble || partials.numel() % 2 || trust.scalar_type() != at::kFloat ||
+      trust.numel() < 1)
+    throw std::runtime_error("Reducer::arm_lars: table (bytes), partials (float64 [chunks][2]) and trust "
+                             "(fp32 [segments]) must be contiguous device tensors");
+  const int64_t nseg = trust.numel(), nchunks = partials.numel() / 2;
+  if (nseg >= (int64_t(1) << 30) || nchunks >= (int64_t(1) << 30) ||
+      table.numel() != nseg * (int64_t)lars_entry_bytes() + nchunks * (int64_t)lars_chunk_entry_bytes() ||
+      ((uintptr_t)table.data_ptr() & 15))
+    throw std::runtime_error("Reducer::arm_lars: table size does not match trust and partials");
+  if (bucket_ranges.size() != st_->flats.size())
+    throw std::runtime_error("Reducer::arm_lars: one segment range per bucket");
+  std::vector<std::array<int, 3>> ranges;
+  int64_t next = 0;
+  for (const auto& r : bucket_ranges) {
+    // buckets are lists of whole parameters in flat order: consecutive segment ranges
+    if (r[0] != next || r[1] < r[0] || r[1] > nseg || r[2] < 0 || r[2] > nchunks)
+      throw std::runtime_error("Reducer::arm_lars: bucket segment ranges must tile [0, segments)");
+    next = r[1];
+    ranges.push_back({(int)r[0], (int)r[1], (int)r[2]});
+  }
+  if (next != nseg) throw std::runtime_error("Reducer::arm_lars: bucket segment ranges must tile [0, segments)");
+  st_->lars.table = table.data_ptr();
+  st_->lars.nseg = (int)nseg;
+  st_->lars.nchunks = (int)nchunks;
+  st_->lars.numel = st_->grad_flat.numel();
+  st_->lars.partials = partials.data_ptr<double>();
+  st_->lars.trust = trust.data_ptr<float>();
+  st_->lars_table = table;
+  st_->lars_partials = partials;
+  st_->lars_trust = trust;
+  st_->lars_wd = weight_decay;
+  st_->lars_eta = eta;
+  st_->lars_eps = eps;
+  st_->lars_ranges = std::move(ranges);
+  st_->lars_on = true;
 }
 
 std::pair<int64_t, int64_t> Reducer::optimizer_applied() const { return st_->sgd_last; }

@@ -30,6 +30,7 @@
 #include <ATen/ATen.h>
 #include <pybind11/pybind11.h>
 
+#include <array>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -77,6 +78,14 @@ class Reducer {
   // mirror_bf16 -- the flat bf16 weight mirror the SGD kernel also writes -- may be undefined)
   void arm_optimizer(double lr, double momentum, double dampening, double weight_decay, bool nesterov,
                      bool first, const at::Tensor& momentum_buf, const at::Tensor& mirror_bf16);
+  // optional, after arm_optimizer: make the armed update LARS (kernels/lars.hip).  table / partials /
+  // trust are the flat space's segment table and work buffers; bucket_ranges[b] = (seg_lo, seg_hi,
+  // chunks of that range) for every bucket -- buckets are lists of whole parameters, so each is a
+  // contiguous segment range.  The three LARS passes for a bucket run where its fused SGD would.
+  // Without this call the armed update is the plain SGD.
+  void arm_lars(const at::Tensor& table, const at::Tensor& partials, const at::Tensor& trust,
+                double weight_decay, double eta, double eps,
+                const std::vector<std::array<int64_t, 3>>& bucket_ranges);
   // (buckets updated by the last finished backward, grad_flat's version counter at its end);
   // (-1, -1) when it applied none or the result was consumed
   std::pair<int64_t, int64_t> optimizer_applied() const;

@@ -59,6 +59,13 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// float64 sibling (same butterfly, so the tree is fixed: bitwise-reproducible sums)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 // Sum over the 16 lanes of a DPP row (lanes 16r..16r+15), result in every lane of the row.
 // Four v_add_f32 with DPP modifiers (quad_perm xor1, xor2, row_ror 4, row_ror 8): no LDS traffic,
 // unlike __shfl_xor which lowers to ds_swizzle / ds_bpermute.

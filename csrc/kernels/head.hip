@@ -8,13 +8,17 @@
 
 namespace pdt {
 
-// one 256-thread block per row
+// one 256-thread block per row.  SMOOTH (label smoothing eps != 0): the pass that sums the
+// exponentials also sums the logits; SMOOTH = false is the unsmoothed kernel, instruction for
+// instruction.
+template <bool SMOOTH>
 __global__ void __launch_bounds__(256) softmax_xent_kernel(const float* __restrict__ logits,
                                                            const int64_t* __restrict__ labels,
                                                            float* __restrict__ dlogits,
                                                            float* __restrict__ row_loss, int V,
-                                                           float invN) {
+                                                           float invN, float eps) {
   __shared__ float red[4];
+  __shared__ float redx[4];
   const int row = blockIdx.x;
   const float* x = logits + (int64_t)row * V;
   float* g = dlogits + (int64_t)row * V;
@@ -26,19 +30,40 @@ __global__ void __launch_bounds__(256) softmax_xent_kernel(const float* __restri
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
-  float s = 0.f;
-  for (int i = t; i < V; i += 256) s += __expf(x[i] - m);
+  float s = 0.f, sx = 0.f;
+  for (int i = t; i < V; i += 256) {
+    const float xi = x[i];
+    s += __expf(xi - m);
+    if (SMOOTH) sx += xi;
+  }
   s = wave_sum(s);
-  if (lane == 0) red[wid] = s;
+  if (SMOOTH) sx = wave_sum(sx);
+  if (lane == 0) {
+    red[wid] = s;
+    if (SMOOTH) redx[wid] = sx;
+  }
   __syncthreads();
   s = red[0] + red[1] + red[2] + red[3];
   const float inv_s = 1.f / s;
   const int64_t lab = labels[row];
-  for (int i = t; i < V; i += 256) {
-    float p = __expf(x[i] - m) * inv_s;
-    g[i] = (p - (i == lab ? 1.f : 0.f)) * invN;
+  if (SMOOTH) {
+    const float hit = 1.f - eps, miss = eps / (float)V;
+    for (int i = t; i < V; i += 256) {
+      float p = __expf(x[i] - m) * inv_s;
+      g[i] = (p - (i == lab ? hit : 0.f) - miss) * invN;
+    }
+    if (t == 0) {
+      sx = redx[0] + redx[1] + redx[2] + redx[3];
+      const float lse = logf(s) + m;
+      row_loss[row] = hit * (lse - x[lab]) + eps * (lse - sx / (float)V);
+    }
+  } else {
+    for (int i = t; i < V; i += 256) {
+      float p = __expf(x[i] - m) * inv_s;
+      g[i] = (p - (i == lab ? 1.f : 0.f)) * invN;
+    }
+    if (t == 0) row_loss[row] = (logf(s) + m - x[lab]);
   }
-  if (t == 0) row_loss[row] = (logf(s) + m - x[lab]);
 }
 
 // deterministic mean of the per-row losses (single block)
@@ -54,9 +79,13 @@ __global__ void __launch_bounds__(256) mean_kernel(const float* __restrict__ v, 
 }
 
 void launch_softmax_xent(const float* logits, const int64_t* labels, float* loss, float* dlogits,
-                         float* ws, int N, int V, hipStream_t st) {
-  hipLaunchKernelGGL(softmax_xent_kernel, dim3(N), dim3(256), 0, st, logits, labels, dlogits, ws, V,
-                     1.f / (float)N);
+                         float* ws, int N, int V, hipStream_t st, float label_smoothing) {
+  if (label_smoothing != 0.f)
+    hipLaunchKernelGGL(softmax_xent_kernel<true>, dim3(N), dim3(256), 0, st, logits, labels, dlogits, ws, V,
+                       1.f / (float)N, label_smoothing);
+  else
+    hipLaunchKernelGGL(softmax_xent_kernel<false>, dim3(N), dim3(256), 0, st, logits, labels, dlogits, ws, V,
+                       1.f / (float)N, 0.f);
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, st, ws, N, loss);
 }
 

@@ -253,8 +253,11 @@ void launch_fc_colsum(const float* g, int rows, int cols, const float* alpha, fl
 
 // ---------------------------------------------------------------- head.hip
 // loss[0] = mean CE, dlogits = (softmax - onehot)/N ; ws >= N floats
+// label_smoothing eps != 0 (torch.nn.functional.cross_entropy semantics): row loss
+// (1-eps)(lse - x[label]) + eps(lse - mean(x)), dlogits = (softmax - (1-eps) onehot - eps/V)/N;
+// eps == 0 launches the unsmoothed kernel
 void launch_softmax_xent(const float* logits, const int64_t* labels, float* loss, float* dlogits,
-                         float* ws, int N, int V, hipStream_t st);
+                         float* ws, int N, int V, hipStream_t st, float label_smoothing = 0.f);
 void launch_top1(const float* logits, const int64_t* labels, int64_t* count, int N, int V,
                  hipStream_t st);
 // x[i] += 1 (the BatchNorm num_batches_tracked counters, one flat int64 buffer)
@@ -270,6 +273,42 @@ void launch_sgd(float* p, const float* g, float* buf, int64_t n, float lr, float
 // fp32 -> bf16 cast (used for bf16 gradient buckets) and back
 void launch_cast_f32_bf16(const float* x, uint16_t* y, int64_t n, hipStream_t st);
 void launch_cast_bf16_f32(const uint16_t* x, float* y, int64_t n, float scale, hipStream_t st);
+
+// ---------------------------------------------------------------- lars.hip
+// LARS (layer-wise trust ratios, then the SGD update of sgd.hip) over one flat fp32 space.
+// table = device bytes: nseg LarsSeg entries (one per parameter tensor, in flat order), then
+// nchunks LarsChunk entries (every segment cut into chunks of <= lars_chunk_elems() elements; a
+// chunk never crosses a segment).  Offsets are elements from the flat bases.
+struct LarsSeg { int64_t off, numel; int32_t chunk0, nchunks, flags, pad; };  // flags bit 0: excluded
+struct LarsChunk { int64_t start; int32_t n; int32_t seg; };
+struct LarsSpace {
+  const void* table;
+  int nseg, nchunks;   // entries in the table
+  int64_t numel;       // elements of the flat buffers (chunks outside are skipped)
+  double* partials;    // [nchunks][2] = (sum p^2, sum g^2) per chunk
+  float* trust;        // [nseg]
+};
+size_t lars_entry_bytes();
+size_t lars_chunk_entry_bytes();
+int lars_chunk_elems();
+// Every launcher covers the segments [seg_lo, seg_hi); the chunk range is read from the table on
+// the device, max_chunks (>= the chunks of that range, e.g. nchunks) only sizes the grid.  The
+// sums use a fixed tree per chunk and a fixed order over a segment's chunks, so the results do not
+// depend on the grid, the stream or the segment range a launch covers.
+void launch_lars_norms(const float* p, const float* g, const LarsSpace& sp, int seg_lo, int seg_hi,
+                       int max_chunks, hipStream_t st);
+// trust[seg] = excluded or |p| == 0 or |g| == 0 ? 1 : float(eta |p| / (|g| + wd |p| + eps)), in float64
+void launch_lars_trust(const LarsSpace& sp, int seg_lo, int seg_hi, double wd, double eta, double eps,
+                       hipStream_t st);
+// d = trust[seg] (g + wd_eff p), wd_eff = excluded ? 0 : wd; then momentum / Nesterov / p -= lr d
+// exactly as launch_sgd (p_bf16: the bf16 mirror side output)
+void launch_lars_update(float* p, const float* g, float* buf, const LarsSpace& sp, int seg_lo, int seg_hi,
+                        int max_chunks, float lr, float momentum, float dampening, float wd, bool nesterov,
+                        bool first, hipStream_t st, uint16_t* p_bf16 = nullptr);
+// norms, trust, update
+void launch_lars(float* p, const float* g, float* buf, const LarsSpace& sp, int seg_lo, int seg_hi,
+                 int max_chunks, float lr, float momentum, float dampening, double wd, bool nesterov,
+                 bool first, double eta, double eps, hipStream_t st, uint16_t* p_bf16 = nullptr);
 
 // ------------------------------------------------------------- augment.hip
 // Fused gather + RandomCrop(pad) + RandomHorizontalFlip + (/255) + Normalize of a device-resident

@@ -600,11 +600,15 @@ def avgpool_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) ->
 # ----------------------------------------------------------------------------
 class _SoftmaxXent(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, label_smoothing=0.0):
         if logits.is_cuda:
-            loss, dlogits = native().softmax_xent(logits.contiguous(), labels.contiguous())
+            if label_smoothing == 0.0:
+                loss, dlogits = native().softmax_xent(logits.contiguous(), labels.contiguous())
+            else:
+                loss, dlogits = native().softmax_xent(logits.contiguous(), labels.contiguous(),
+                                                      float(label_smoothing))
         else:
-            loss, dlogits = ref.softmax_xent(logits, labels)
+            loss, dlogits = ref.softmax_xent(logits, labels, label_smoothing)
         ctx.save_for_backward(dlogits)
         return loss
 
@@ -612,19 +616,26 @@ class _SoftmaxXent(torch.autograd.Function):
     def backward(ctx, dloss):
         (dlogits,) = ctx.saved_tensors
         if dlogits.is_cuda:  # scaled on the device by the (device) loss gradient: no host sync
-            return native().scale_by(dlogits, dloss.float().reshape(1)), None
-        return dlogits * dloss, None
+            return native().scale_by(dlogits, dloss.float().reshape(1)), None, None
+        return dlogits * dloss, None, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-    return _SoftmaxXent.apply(logits, labels)
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean cross entropy; ``label_smoothing`` as in ``torch.nn.functional.cross_entropy``."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    return _SoftmaxXent.apply(logits, labels, label_smoothing)
 
 
 class CrossEntropyLoss(nn.Module):
     """Drop-in for ``nn.CrossEntropyLoss()`` (mean reduction, ``resnet/main.py:102``)."""
 
+    def __init__(self, label_smoothing: float = 0.0):
+        super().__init__()
+        self.label_smoothing = float(label_smoothing)
+
     def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        return cross_entropy(logits, labels)
+        return cross_entropy(logits, labels, self.label_smoothing)
 
 
 def top1_correct(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

@@ -111,12 +111,20 @@ def global_avgpool(x: torch.Tensor) -> torch.Tensor:
     return x.float().mean(dim=(1, 2))
 
 
-def softmax_xent(logits: torch.Tensor, labels: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Mean-reduced cross entropy and its gradient w.r.t. logits."""
+def softmax_xent(logits: torch.Tensor, labels: torch.Tensor,
+                 label_smoothing: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Mean-reduced cross entropy and its gradient w.r.t. logits.  ``label_smoothing`` eps as in
+    ``F.cross_entropy``: the target is (1-eps) onehot + eps/V, so the gradient is
+    (softmax - (1-eps) onehot - eps/V) / N."""
     lf = logits.float()
-    loss = F.cross_entropy(lf, labels)
-    p = torch.softmax(lf, dim=1)
-    p[torch.arange(lf.shape[0]), labels] -= 1.0
+    if label_smoothing == 0.0:
+        loss = F.cross_entropy(lf, labels)
+        p = torch.softmax(lf, dim=1)
+        p[torch.arange(lf.shape[0]), labels] -= 1.0
+        return loss, p / lf.shape[0]
+    loss = F.cross_entropy(lf, labels, label_smoothing=label_smoothing)
+    p = torch.softmax(lf, dim=1) - label_smoothing / lf.shape[1]
+    p[torch.arange(lf.shape[0]), labels] -= 1.0 - label_smoothing
     return loss, p / lf.shape[0]
 
 
@@ -138,3 +146,34 @@ def sgd_momentum_(params, grads, bufs, lr: float, momentum: float, dampening: fl
                 b.mul_(momentum).add_(d, alpha=1 - dampening)
             d = d.add(b, alpha=momentum) if nesterov else b
         p.add_(d, alpha=-lr)
+
+
+def lars_trust_ratio(p: torch.Tensor, g: torch.Tensor, weight_decay: float, eta: float, eps: float,
+                     excluded: bool) -> float:
+    """Layer-wise trust ratio: float32(eta |p| / (|g| + wd |p| + eps)) with the norms and the
+    expression in float64; 1 for an excluded tensor and for a zero parameter or gradient norm."""
+    if excluded:
+        return 1.0
+    pn = float(p.detach().double().pow(2).sum().sqrt())
+    gn = float(g.detach().double().pow(2).sum().sqrt())
+    if pn == 0 or gn == 0:
+        return 1.0
+    return float(torch.tensor(eta * pn / (gn + weight_decay * pn + eps), dtype=torch.float64).float())
+
+
+def lars_momentum_(params, grads, bufs, lr: float, momentum: float, dampening: float,
+                   weight_decay: float, nesterov: bool, first_step: bool, eta: float = 1e-3,
+                   eps: float = 1e-8, exclude_1d: bool = True):
+    """LARS as "rescale the gradient, then SGD" on lists of tensors: per tensor
+    ``d = trust * (g + wd_eff * p)`` and then ``sgd_momentum_``'s momentum / Nesterov / update, so
+    ``bufs`` keep torch.optim.SGD's meaning.  ``exclude_1d``: tensors with ``ndim <= 1`` (BatchNorm
+    weights and biases, the fc bias) get neither weight decay nor the trust ratio."""
+    for p, g, b in zip(params, grads, bufs):
+        excluded = bool(exclude_1d and p.ndim <= 1)
+        trust = lars_trust_ratio(p, g, weight_decay, eta, eps, excluded)
+        d = g
+        if weight_decay != 0 and not excluded:
+            d = d.add(p, alpha=weight_decay)
+        if trust != 1.0:
+            d = d * trust
+        sgd_momentum_([p], [d], [b], lr, momentum, dampening, 0.0, nesterov, first_step)

@@ -1,1 +1,3 @@
+from .lars import LARS  # noqa: F401
+from .schedule import WarmupPolyLR  # noqa: F401
 from .sgd import SGD  # noqa: F401

@@ -91,7 +91,7 @@ class SGD(torch.optim.Optimizer):
         if sp is None:
             return
         hp = self._hyper(group)
-        lr, mom, damp, wd, nest = hp
+        lr, mom, damp, wd, nest = hp[:5]  # (a subclass may append its own hyperparameters)
         buf, first = self._flat_momentum(sp, mom)
         mirror = sp.mirror()
         reducer.arm_optimizer(lr, mom, damp, wd, nest, first, buf, mirror.krsc if mirror is not None else None)
@@ -139,8 +139,7 @@ class SGD(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         for group in self.param_groups:
-            lr, mom, damp = group["lr"], group["momentum"], group["dampening"]
-            wd, nest = group["weight_decay"], group["nesterov"]
+            mom = group["momentum"]
             sp = self._flat_space_of(group)
             if sp is not None and sp.param_flat.is_cuda:
                 mirror = sp.mirror()
@@ -153,8 +152,7 @@ class SGD(torch.optim.Optimizer):
                 if not sp.grads_attached():
                     sp.gather_grads()
                 buf, first = self._flat_momentum(sp, mom)
-                native().sgd_step(sp.param_flat, sp.grad_flat, buf, lr, mom, damp, wd, nest,
-                                  first, 1.0, mirror.krsc if mirror is not None else None)
+                self._flat_update(sp, group, buf, first, mirror.krsc if mirror is not None else None)
                 self._flat_first[id(sp)] = False
                 if mirror is not None:
                     mirror.after_optimizer_step()  # bf16 conv weights for the next forward
@@ -172,9 +170,19 @@ class SGD(torch.optim.Optimizer):
                 bufs.append(st.get("momentum_buffer"))
                 firsts.append(first)
             for p, g, b, f in zip(params, grads, bufs, firsts):
-                ref.sgd_momentum_(
-                    [p], [g], [b], lr, mom, damp, wd, nest, f)
+                self._tensor_update(group, p, g, b, f)
         return loss
+
+    # the two update rules a subclass replaces (optim.LARS); everything around them is shared
+    def _flat_update(self, sp, group, buf, first, krsc) -> None:
+        """One fused pass over a GPU flat space (``krsc``: the bf16 mirror side output or None)."""
+        native().sgd_step(sp.param_flat, sp.grad_flat, buf, group["lr"], group["momentum"], group["dampening"],
+                          group["weight_decay"], group["nesterov"], first, 1.0, krsc)
+
+    def _tensor_update(self, group, p, g, buf, first) -> None:
+        """One tensor outside a GPU flat space (CPU, or a group that is not a flat space)."""
+        ref.sgd_momentum_([p], [g], [buf], group["lr"], group["momentum"], group["dampening"],
+                          group["weight_decay"], group["nesterov"], first)
 
     def _overlap_step(self, sp, group) -> bool:
         """True if the last backward applied this step per bucket; validates the contract."""

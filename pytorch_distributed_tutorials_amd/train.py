@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import ops
 from .data import DeviceLoader, DistributedSampler, build_dataset
 from .models import build_model
-from .optim import SGD
+from .optim import LARS, SGD, WarmupPolyLR
 from .parallel import DistributedDataParallel, destroy, init_distributed
 from .parallel.comm import CommOptions
 from .utils.checkpoint import load_checkpoint, save_checkpoint
@@ -98,6 +98,21 @@ def build_parser() -> argparse.ArgumentParser:
                    help="native impl on a GPU: capture the whole training step (forward, backward with "
                         "the bucketed all-reduces, SGD) in a HIP graph once and replay it for every "
                         "full-size batch; the launch-bound ResNet-18/CIFAR step gains the most")
+    # ---- large-batch recipe (the defaults are the reference's plain SGD at a constant rate)
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                   help="lars = layer-wise trust ratios on top of SGD with momentum (optim.LARS)")
+    p.add_argument("--momentum", type=float, default=0.9)
+    p.add_argument("--weight-decay", type=float, default=1e-5)
+    p.add_argument("--trust-coefficient", type=float, default=1e-3, help="LARS eta")
+    p.add_argument("--lars-eps", type=float, default=1e-8)
+    p.add_argument("--lars-adapt-1d", action="store_true",
+                   help="LARS: also decay and adapt BatchNorm parameters and biases (exclude_1d off)")
+    p.add_argument("--label-smoothing", type=float, default=0.0)
+    p.add_argument("--lr-schedule", default="constant", choices=["constant", "warmup-poly"],
+                   help="warmup-poly: linear warm-up over --warmup-epochs to --learning_rate, then "
+                        "polynomial (power 2) decay to --lr-end at the end of --num_epochs")
+    p.add_argument("--warmup-epochs", type=float, default=5.0)
+    p.add_argument("--lr-end", type=float, default=0.0)
     return p
 
 
@@ -185,6 +200,11 @@ def evaluate(model: nn.Module, device: torch.device, test_loader) -> float:
 
 def main(argv: Optional[list] = None) -> int:
     args = build_parser().parse_args(argv)
+    if args.graph and args.lr_schedule != "constant":
+        # the captured step bakes lr in as a kernel argument: _GraphStep would capture again every step
+        raise SystemExit(f"--graph cannot follow --lr-schedule {args.lr_schedule}: the captured step bakes "
+                         "the learning rate in, so a schedule would re-capture it every step; use "
+                         "--lr-schedule constant with --graph")
     set_random_seeds(args.seed, deterministic=args.deterministic)
     env = init_distributed(args.backend, args.local_rank, args.timeout)
     local_rank = env.local_rank
@@ -233,15 +253,25 @@ def main(argv: Optional[list] = None) -> int:
                                         bucket_cap_mb=args.bucket_mb, wire_dtype=args.wire_dtype,
                                         comm_options=CommOptions.from_env(timeout=args.timeout))
     holder["ddp"] = ddp_model
-    criterion = ops.CrossEntropyLoss() if impl == "native" else nn.CrossEntropyLoss()
+    if args.label_smoothing != 0.0:
+        criterion = ops.CrossEntropyLoss(label_smoothing=args.label_smoothing) if impl == "native" \
+            else nn.CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    else:
+        criterion = ops.CrossEntropyLoss() if impl == "native" else nn.CrossEntropyLoss()
     timer = StepTimer(device, ddp_model)
     if args.log_every:
         ddp_model.enable_comm_timing(True)
     inject = FaultInjector(env.rank)
     # a captured step keeps the post-backward update (the per-bucket one's local-mode reducer made
     # graph replay ~2.7x slower, bench.py --graph)
-    optimizer = SGD(ddp_model.parameters(), lr=args.learning_rate, momentum=0.9, weight_decay=1e-5,
-                    overlap=False if args.graph else None)
+    if args.optimizer == "lars":
+        optimizer = LARS(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
+                         weight_decay=args.weight_decay, trust_coefficient=args.trust_coefficient,
+                         eps=args.lars_eps, exclude_1d=not args.lars_adapt_1d,
+                         overlap=False if args.graph else None)
+    else:
+        optimizer = SGD(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
+                        weight_decay=args.weight_decay, overlap=False if args.graph else None)
 
     model_filepath = os.path.join(args.model_dir, args.model_filename)
     start_epoch = 0
@@ -265,7 +295,17 @@ def main(argv: Optional[list] = None) -> int:
 
     graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1) \
         if args.graph else None
-    global_step = 0
+    steps_per_epoch = len(train_loader)
+    if args.max_steps_per_epoch is not None:
+        steps_per_epoch = min(steps_per_epoch, args.max_steps_per_epoch)
+    # a resumed run continues the step count (and with it the stateless schedule) where it stopped
+    global_step = start_epoch * steps_per_epoch
+    schedule = None
+    if args.lr_schedule == "warmup-poly":
+        total = max(args.num_epochs * steps_per_epoch, 1)
+        schedule = WarmupPolyLR(optimizer, args.learning_rate,
+                                min(int(round(args.warmup_epochs * steps_per_epoch)), total), total,
+                                power=2.0, end_lr=args.lr_end)
     done = False
     for epoch in range(start_epoch, args.num_epochs):
         print("Local Rank: {}, Epoch: {}, Training ...".format(local_rank, epoch), flush=True)
@@ -301,6 +341,11 @@ def main(argv: Optional[list] = None) -> int:
                 watchdog.heartbeat(f"epoch {epoch} step {step}")
             inject(global_step)
             inputs, labels = inputs.to(device), labels.to(device)
+            if schedule is not None:
+                # before the forward: the per-bucket update is armed with the rate it has there
+                lr = schedule.set(global_step)
+                if step == 0 and env.rank == 0:
+                    print("Epoch: {}, step: {}, lr: {!r}".format(epoch, global_step, lr), flush=True)
             if graph_step is not None:
                 with trace.trace_range("step"):
                     loss = graph_step(inputs, labels)
