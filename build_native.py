@@ -5,13 +5,14 @@
 
 * every ``csrc/kernels/*.hip`` is compiled by ``hipcc --offload-arch=gfx950``
   WITHOUT PyTorch headers (fast, seconds per file);
-* ``csrc/bindings.cpp``, ``csrc/comm/*.cpp`` and ``csrc/ddp/*.cpp`` are host C++
-  compiled by hipcc against the installed PyTorch headers;
+* ``csrc/*.cpp`` (the module and one binding source per op family), ``csrc/comm/*.cpp``
+  and ``csrc/ddp/*.cpp`` are host C++ compiled by hipcc against the installed PyTorch headers;
 * everything is linked into ``pytorch_distributed_tutorials_amd/_C<EXT_SUFFIX>``
   against libtorch and the RCCL shipped inside the torch wheel, rpath'd to it.
 
 Incremental: an object is rebuilt when its source or any header under csrc/ is
-newer.  Works without a GPU (hipcc cross-compiles), so it runs in CI/CPU boxes.
+newer, and an object whose source is gone is deleted (other tools link every object of the build
+directory).  Works without a GPU (hipcc cross-compiles), so it runs in CI/CPU boxes.
 
 ``--sanitize``: a host-side AddressSanitizer + UndefinedBehaviorSanitizer build (``-O1 -g``,
 ``-fsanitize=address,undefined`` on the host compilation only -- GPU code stays uninstrumented)
@@ -78,7 +79,7 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
     common = ["-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1",
               "-Wno-unused-result", "-Wno-unused-value"] + opt
     kern_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
-    host_srcs = [os.path.join(CSRC, "bindings.cpp")] + sorted(
+    host_srcs = sorted(glob.glob(os.path.join(CSRC, "*.cpp"))) + sorted(
         glob.glob(os.path.join(CSRC, "comm", "*.cpp")) + glob.glob(os.path.join(CSRC, "ddp", "*.cpp")))
     py_inc = sysconfig.get_paths()["include"]
     host_flags = common + [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C",
@@ -109,6 +110,8 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                 f.result()
                 if verbose:
                     print(f"[build_native]   ok {os.path.relpath(futs[f], ROOT)}", flush=True)
+    for old in set(glob.glob(os.path.join(bdir, "*.o"))) - set(objs):
+        os.remove(old)  # its source was removed or renamed
     so = asan_out_path() if sanitize else out_path()
     os.makedirs(os.path.dirname(so), exist_ok=True)
     if force or jobs_list or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(o) for o in objs):
