@@ -28,12 +28,9 @@ from ..utils.seed import deterministic
 from ._ext import native
 
 _CPU_DTYPE = torch.float32  # activation dtype of the CPU reference path
-# fused-backward switches (module constants; the unfused paths stay for the CPU reference and
-# the fallbacks): BN backward inside the dgrad epilogue, and its cross-block handoff
-_FUSE_DGRAD_BN = True
-_BN_HANDOFF = True
-_ZMASK = True  # 1-bit ReLU masks for the handoff (else read z)
+# Module switches: the ones tests, scripts or the README's knob table set.
 _NAN_TRACE = os.environ.get("PDT_NAN_TRACE", "0") == "1"  # debug: report NaN in saved tensors
+_STEM_POOL = True  # debugging switch (default on): BN + ReLU + max pool of the stem in one pass
 _FP8 = False  # forward convolutions on the MX-rate fp8 MFMA (set_fp8)
 _FP8_BWD = True  # with fp8: also the input-gradient GEMMs
 # with fp8 backward: weight gradients on the MX-rate MFMA from the e5m2 dy and the e4m3 conv input
@@ -42,6 +39,8 @@ _FP8_WGRAD = True
 # fp8-only storage: activations / input gradients whose every consumer reads the fp8 copy are not
 # written in bf16 at all (interior bottleneck outputs, and dy of convs with fp8 dgrad + fp8 wgrad)
 _FP8_ONLY = True
+_FP8_KMIN = 128  # least GEMM K of an fp8 forward conv (_fp8_conv_ok)
+_FP8_DGRAD_NARROW = True  # fp8 input gradients also for k % 16 channels at stride 1 (_fp8_dgrad_ok)
 # _BN_ACC (non-deterministic runs only; deterministic runs always take the partial buffers):
 # BN-backward sums of a BN-fused dgrad accumulated by its epilogue's fp32 atomics into a per-BN
 # [2, C] buffer -- no partial buffer and no reduce launch on the main stream; the consuming apply
@@ -49,6 +48,24 @@ _FP8_ONLY = True
 # once the apply is done.  Round 3 measured it neutral (r3t); with round 4's kernels it pays
 # (r4ab, interleaved: 18.78 / 18.72 ms on vs 18.86 / 18.85 off), so on.
 _BN_ACC = True
+# the projection-shortcut BN's backward sums taken in the next block's hand-off dgrad epilogue (the
+# same output gradient g feeds both BNs of a downsampling block): no reduction pass over g and y_ds
+_DUAL_BN = os.environ.get("PDT_DUAL_BN", "1") == "1"  # (A/B knob)
+DUAL_CALLS = 0  # shortcut BNs whose backward sums came from the hand-off epilogue (tests)
+# Fold the last unit's BN backward into its 1x1 input gradient (DgradFold) -- ResNet-50 b256 in the
+# same calls: 18.15 vs 18.29 and 18.27 vs 18.54 ms/step (r6r / r6s); removing that apply altogether
+# bounds the gain at 1.47 ms (r6f), the rest is spent in the fold-weight kernels on the critical
+# stream (~20 us per block in-step) and the larger dgrad K.
+_FOLD_BN = True
+FOLD_CALLS = 0  # folded units so far (tests check that the path engaged)
+# test hook (tests/test_blocks_gpu.py, mask-matched reference): when a list, every fused block
+# forward appends its units' stored post-activation outputs (z, NHWC bf16), so an fp32 reference
+# can take the native path's ReLU decisions and compare gradients without ReLU-flip noise
+_CAPTURE = None
+# diagnostic hook (bench.py PDT_DIAG_LEAD=1): when a list, every block forward / backward appends
+# (tag, host perf_counter, timing event recorded on the current stream at its entry), so the host's
+# lead over the device can be read per block after the run
+_LEAD = None
 
 
 def _bacc(p, c):
@@ -71,29 +88,11 @@ def _facc(p, c):
     return a
 
 
-_FUSE_RES_BN = True  # shortcut BN applied in the block tail
-# test hook (tests/test_blocks_gpu.py, mask-matched reference): when a list, every fused block
-# forward appends its units' stored post-activation outputs (z, NHWC bf16), so an fp32 reference
-# can take the native path's ReLU decisions and compare gradients without ReLU-flip noise
-_CAPTURE = None
-# diagnostic hook (bench.py PDT_DIAG_LEAD=1): when a list, every block forward / backward appends
-# (tag, host perf_counter, timing event recorded on the current stream at its entry), so the host's
-# lead over the device can be read per block after the run
-_LEAD = None
-
-
 def _lead_mark(tag: str) -> None:
     import time
     ev = torch.cuda.Event(enable_timing=True)
     ev.record()
     _LEAD.append((tag, time.perf_counter(), ev))
-
-
-_COMPACT_ADDEND = True  # stride-2 shortcut dgrad compact
-# the projection-shortcut BN's backward sums taken in the next block's hand-off dgrad epilogue (the
-# same output gradient g feeds both BNs of a downsampling block): no reduction pass over g and y_ds
-_DUAL_BN = os.environ.get("PDT_DUAL_BN", "1") == "1"  # (A/B knob)
-DUAL_CALLS = 0  # shortcut BNs whose backward sums came from the hand-off epilogue (tests)
 
 
 def set_fp8(on: bool) -> None:
@@ -307,6 +306,51 @@ class _ConvBN(torch.autograd.Function):
                 None, None, None, None, None, None, None, None)
 
 
+def _grad_sink(p):
+    """Flat-buffer gradient view to accumulate into, if the parameter lives in a FlatParamSpace."""
+    sp = getattr(p, "_pdt_flat", None)
+    if sp is None or not p.requires_grad or not p.is_cuda:
+        return None
+    return sp.grad_sink(p)
+
+
+def _wgrad_into(p, sunk, fn, *args):
+    """Weight gradient ``fn(*args)`` of parameter ``p``: accumulated into its flat-space gradient sink
+    (``fn(*args, sink)``; p goes to ``sunk`` for ``mark_ready``) -> None, or without one returned in p's dtype."""
+    sink = _grad_sink(p)
+    if sink is None:
+        return fn(*args).to(p.dtype)
+    fn(*args, sink)
+    sunk.append(p)
+    return None
+
+
+def _bn_dest(p_gamma, p_beta, atomic):
+    """Where a BatchNorm's dgamma / dbeta go.  None: no flat-space sinks, autograd gets them back.  Else
+    (acc, sg, sb): into the sinks sg / sb -- by the reducing kernel itself (acc None), or with ``atomic``
+    by the BN's apply pass from the [2, C] accumulator ``acc`` that a dgrad epilogue's atomics fill."""
+    sg, sb = _grad_sink(p_gamma), _grad_sink(p_beta)
+    if sg is None or sb is None:
+        return None
+    return (_bacc(p_gamma, p_gamma.shape[0]) if atomic else None), sg, sb
+
+
+def _stem_conv_stats(C, x, weight, gamma, beta, running_mean, running_var, stride, pad, training, momentum, eps):
+    """Super-pixel stem conv -> BN statistics (finalize + running-stat update, or the eval
+    parameters): (xsp, y, part, stats[4, K])."""
+    xsp, y, part, grows = C.stem_conv_fwd(x, weight, stride, pad, training)
+    count = y.shape[0] * y.shape[1] * y.shape[2]
+    buffers_ready()
+    if training:
+        if running_mean is None:
+            running_mean = torch.zeros(weight.shape[0], device=x.device)
+            running_var = torch.ones(weight.shape[0], device=x.device)
+        stats = C.bn_finalize(part, count, running_mean, running_var, gamma, beta, float(momentum), float(eps), grows)
+    else:
+        stats = C.bn_eval_params(running_mean, running_var, gamma, beta, float(eps))
+    return xsp, y, part, stats
+
+
 class _StemConvBN(torch.autograd.Function):
     """Device stem: NCHW fp32 image -> conv 7x7/s2 -> BN -> ReLU as a super-pixel conv.
 
@@ -320,18 +364,8 @@ class _StemConvBN(torch.autograd.Function):
     def forward(ctx, x, weight, gamma, beta, running_mean, running_var, stride, pad, training,
                 momentum, eps):
         C = native()
-        xsp, y, part, grows = C.stem_conv_fwd(x, weight, stride, pad, training)
-        k = weight.shape[0]
-        count = y.shape[0] * y.shape[1] * y.shape[2]
-        buffers_ready()
-        if training:
-            if running_mean is None:
-                running_mean = torch.zeros(k, device=x.device)
-                running_var = torch.ones(k, device=x.device)
-            stats = C.bn_finalize(part, count, running_mean, running_var, gamma, beta,
-                                  float(momentum), float(eps), grows)
-        else:
-            stats = C.bn_eval_params(running_mean, running_var, gamma, beta, float(eps))
+        xsp, y, part, stats = _stem_conv_stats(C, x, weight, gamma, beta, running_mean, running_var, stride, pad,
+                                               training, momentum, eps)
         z = C.bn_act_fwd(y, stats[2], stats[3], None, True)
         _nan_trace("stem", x=x, xsp=xsp, y=y, part=part, stats=stats, z=z)
         ctx.save_for_backward(xsp, y, stats, gamma)
@@ -350,12 +384,10 @@ class _StemConvBN(torch.autograd.Function):
         dy, _ = C.bn_act_bwd_apply(dz, dz, y, stats, gamma, sums, 2, ctx.training, False)
         dw = None
         if ctx.needs_input_grad[1]:
-            sink = _grad_sink(weight)
-            if sink is not None:
-                C.stem_wgrad(dy, xsp, list(weight.shape), deterministic(), sink)
-                weight._pdt_flat.mark_ready([weight])
-            else:
-                dw = C.stem_wgrad(dy, xsp, list(weight.shape), deterministic()).to(weight.dtype)
+            sunk = []
+            dw = _wgrad_into(weight, sunk, C.stem_wgrad, dy, xsp, list(weight.shape), deterministic())
+            if sunk:
+                weight._pdt_flat.mark_ready(sunk)
         ctx.weight = None
         return (None, dw, dgamma.to(gamma.dtype), dbeta.to(gamma.dtype), None, None, None, None,
                 None, None, None)
@@ -384,19 +416,9 @@ class _StemConvBNPool(torch.autograd.Function):
     def forward(ctx, x, weight, gamma, beta, running_mean, running_var, stride, pad, training,
                 momentum, eps):
         C = native()
-        xsp, y, part, grows = C.stem_conv_fwd(x, weight, stride, pad, training)
-        k = weight.shape[0]
-        count = y.shape[0] * y.shape[1] * y.shape[2]
-        buffers_ready()
-        if training:
-            if running_mean is None:
-                running_mean = torch.zeros(k, device=x.device)
-                running_var = torch.ones(k, device=x.device)
-            stats = C.bn_finalize(part, count, running_mean, running_var, gamma, beta,
-                                  float(momentum), float(eps), grows)
-        else:
-            stats = C.bn_eval_params(running_mean, running_var, gamma, beta, float(eps))
-        if training and _STEM_ARGMAX_Y:
+        xsp, y, part, stats = _stem_conv_stats(C, x, weight, gamma, beta, running_mean, running_var, stride, pad,
+                                               training, momentum, eps)
+        if training:  # also u = y at each window's argmax, for the backward reduction
             out, idx, u = C.bn_relu_maxpool(y, stats[2], stats[3], True)
         else:
             (out, idx), u = C.bn_relu_maxpool(y, stats[2], stats[3]), None
@@ -415,58 +437,38 @@ class _StemConvBNPool(torch.autograd.Function):
         gp, bp = ctx.bn_params
         ctx.bn_params = None
         dout = dout.contiguous()
-        sg, sb = _grad_sink(gp), _grad_sink(bp)
         sunk = []
+        dest = _bn_dest(gp, bp, False)  # with sinks: dgamma / dbeta straight into the flat buffer
+        sinks = dest[1:] if dest is not None else ()
         # BN reduction sum g, sum g*(y - mean): g is nonzero only at window argmaxes, so with u = y at
         # each argmax (saved by the forward pool) it is a plain streaming reduction over the pooled
         # tensors (2 x 103 MB at batch 256) instead of a gather over y (411 MB)
         if u is not None:
-            red = lambda *o: C.bn_act_bwd_reduce(dout, u, u, stats, 2, *o)  # noqa: E731
+            sums = C.bn_act_bwd_reduce(dout, u, u, stats, 2, *sinks)
         else:
-            red = lambda *o: C.pool_bn_bwd_reduce(dout, idx, y, stats, *o)  # noqa: E731
-        if sg is not None and sb is not None:  # BN parameter gradients straight into the flat buffer
-            sums = red(sg, sb)
-            dgamma = dbeta = None
-            sunk += [gp, bp]
-        else:
-            sums = red()
+            sums = C.pool_bn_bwd_reduce(dout, idx, y, stats, *sinks)
+        dgamma = dbeta = None
+        if dest is None:
             dgamma, dbeta = (sums[1] * stats[1]).to(gamma.dtype), sums[0].to(gamma.dtype)
+        else:
+            sunk += [gp, bp]
         dw = None
-        if ctx.needs_input_grad[1] and _STEM_BWD_FUSED and C.stem_bwd_fused_supported(
-                weight.shape[0], weight.shape[2], (weight.shape[3] + 2) // 2, y.shape[1], y.shape[2]):
+        shape = list(weight.shape)
+        if ctx.needs_input_grad[1] and C.stem_bwd_fused_supported(shape[0], shape[2], (shape[3] + 2) // 2,
+                                                                  y.shape[1], y.shape[2]):
             # the image takes no gradient, so dy's only consumer is the weight gradient: the BN/pool
             # backward apply runs inside it and the full-resolution dy is never stored
-            sink = _grad_sink(weight)
-            if sink is not None:
-                C.stem_bwd_fused(dout, idx, y, stats, gamma, sums, ctx.training, xsp, list(weight.shape),
-                                 deterministic(), sink)
-                sunk.append(weight)
-            else:
-                dw = C.stem_bwd_fused(dout, idx, y, stats, gamma, sums, ctx.training, xsp, list(weight.shape),
-                                      deterministic()).to(weight.dtype)
-            if sunk:
-                sunk[0]._pdt_flat.mark_ready(sunk)
-            _end_mirror_trust(weight)
-            ctx.weight = None
-            return (None, dw, dgamma, dbeta, None, None, None, None, None, None, None)
-        dy = C.pool_bn_bwd_apply(dout, idx, y, stats, gamma, sums, ctx.training)
-        if ctx.needs_input_grad[1]:
-            sink = _grad_sink(weight)
-            if sink is not None:
-                C.stem_wgrad(dy, xsp, list(weight.shape), deterministic(), sink)
-                sunk.append(weight)
-            else:
-                dw = C.stem_wgrad(dy, xsp, list(weight.shape), deterministic()).to(weight.dtype)
+            dw = _wgrad_into(weight, sunk, C.stem_bwd_fused, dout, idx, y, stats, gamma, sums, ctx.training,
+                             xsp, shape, deterministic())
+        else:
+            dy = C.pool_bn_bwd_apply(dout, idx, y, stats, gamma, sums, ctx.training)
+            if ctx.needs_input_grad[1]:
+                dw = _wgrad_into(weight, sunk, C.stem_wgrad, dy, xsp, shape, deterministic())
         if sunk:
             sunk[0]._pdt_flat.mark_ready(sunk)
         _end_mirror_trust(weight)
         ctx.weight = None
         return (None, dw, dgamma, dbeta, None, None, None, None, None, None, None)
-
-
-_STEM_POOL = True  # debugging switch (default on)
-_STEM_BWD_FUSED = True  # A/B switch (default on)
-_STEM_ARGMAX_Y = True  # A/B switch (default on)
 
 
 def _stem_fast(x: torch.Tensor, conv: nn.Conv2d) -> bool:
@@ -774,21 +776,56 @@ def _packed_crsk(w):
     return m.crsk_view(w) if m is not None else None
 
 
-def _unit_fwd(C, x, w, gamma, beta, rm, rv, stride, pad, relu, training, momentum, eps, residual,
-              x8=None, q8=None, want_mask=False, want_z=True, csum=None):
-    """conv -> BN -> (+residual) -> (ReLU) -> (z, y, stats, z8, zmask).  x8 = (e4m3 copy of x, its
-    dequant factor): fp8 conv; q8 = _Q8State: also emit the e4m3 copy z8 of the output;
+class _Unit:
+    """One conv + BN unit of a residual block (chain unit or projection shortcut): its configuration,
+    its tensors as the node got them, the Parameter objects p_* (whose flat-space sinks take the
+    gradients), its index ``base`` into ``grads``, and in backward what the forward saved: (z, y,
+    stats) -- z None when fp8-only, and for the shortcut -- and the e4m3 copy x8 of its conv input."""
+
+    __slots__ = ("stride", "pad", "training", "momentum", "eps", "w", "gamma", "beta", "rm", "rv",
+                 "p_w", "p_gamma", "p_beta", "z", "y", "stats", "x8", "base")
+
+
+def _block_units(spec, params, saved=None, in8=None):
+    """(chain units, shortcut unit or None) of one block.  The one place that knows the flat layouts:
+    ``params`` (the node's ``*tensors``, and ``grads``) holds five tensors per unit, chain units
+    first, then the shortcut; ``saved`` (backward: ctx.saved_tensors) holds x, (z, y, stats) per
+    chain unit, (y, stats) of the shortcut, then the saved ``params``; ``in8`` the e4m3 conv inputs
+    of the chain units (the shortcut reads the first one's)."""
+    chain, ds_cfg, _ = spec
+    nch = len(chain)
+    tensors = params if saved is None else saved[len(saved) - len(params):]
+    units = []
+    for i, cfg in enumerate(chain if ds_cfg is None else (*chain, ds_cfg)):
+        u = _Unit()
+        u.base = b = 5 * i
+        u.stride, u.pad, u.training, u.momentum, u.eps = cfg
+        u.w, u.gamma, u.beta, u.rm, u.rv = tensors[b:b + 5]
+        u.p_w, u.p_gamma, u.p_beta = params[b:b + 3]
+        u.z = u.y = u.stats = u.x8 = None
+        if saved is not None and i < nch:
+            u.z, u.y, u.stats = saved[1 + 3 * i:4 + 3 * i]
+        elif saved is not None:
+            u.y, u.stats = saved[1 + 3 * nch:3 + 3 * nch]
+        if in8:
+            u.x8 = in8[i if i < nch else 0]
+        units.append(u)
+    return (units, None) if ds_cfg is None else (units[:nch], units[nch])
+
+
+def _unit_fwd(C, x, u, relu, residual, x8=None, q8=None, want_mask=False, want_z=True, csum=None):
+    """conv -> BN -> (+residual) -> (ReLU) of unit ``u`` -> (z, y, stats, z8, zmask).  x8 = (e4m3
+    copy of x, its dequant factor): fp8 conv; q8 = _Q8State: also emit the e4m3 copy z8 of the output;
     want_mask (with relu): also the 1-bit ReLU mask zmask a later BN-fused dgrad reads instead of z.
     ``residual`` is an activation, or ``(y_short, stats_short)``: a projection shortcut's raw conv
     output and its BN statistics, normalised inside this unit's apply pass (never materialised).
     csum: fp32 [8, k] slots the apply adds the output's per-channel sums into (DgradFold colsum)."""
-    y, stats = _unit_conv_stats(C, x, w, gamma, beta, rm, rv, stride, pad, training, momentum, eps, x8)
-    k = w.shape[0]
+    y, stats = _unit_conv_stats(C, x, u, x8)
+    k = u.w.shape[0]
     rsc = rsh = None
     if isinstance(residual, tuple):
         residual, rst = residual
         rsc, rsh = rst[2], rst[3]
-    want_mask = want_mask and relu
     if q8 is not None and k % 16 == 0:
         assert rsc is None, "fp8 apply takes a materialised residual"
         slot = q8.next_slot()
@@ -801,9 +838,6 @@ def _unit_fwd(C, x, w, gamma, beta, rm, rv, stride, pad, relu, training, momentu
     return z, y, stats, None, None
 
 
-_FP8_KMIN = 128
-
-
 def _fp8_conv_ok(r, s, cx):
     """fp8 forward conv for a GEMM K of r*s*cx >= _FP8_KMIN (K = 64 half-fills the 128-wide fp8
     K-step).  128 (layer2's 1x1 over 128 channels on fp8, so its input needs no bf16 copy) vs 256:
@@ -811,9 +845,6 @@ def _fp8_conv_ok(r, s, cx):
     fp8 too, after the narrow fp8 dgrad) vs 128: b256 16.88 vs 16.77 ms, b512 31.09 vs 30.83 ms
     (r3ap, one box)."""
     return r * s * cx >= _FP8_KMIN
-
-
-_FP8_DGRAD_NARROW = True
 
 
 def _fp8_dgrad_ok(k, stride):
@@ -833,8 +864,10 @@ def _fp8_only_ok(w_next, k, tr):
     return cn == k and k % 16 == 0 and kn % 64 == 0 and _fp8_conv_ok(rn, sn, k)
 
 
-def _unit_conv_stats(C, x, w, gamma, beta, rm, rv, stride, pad, training, momentum, eps, x8=None):
-    """conv -> BN statistics (finalize, running-stat update): (y, stats[4, K])."""
+def _unit_conv_stats(C, x, u, x8=None):
+    """conv -> BN statistics (finalize, running-stat update) of unit ``u``: (y, stats[4, K])."""
+    w, gamma, beta, rm, rv = u.w, u.gamma, u.beta, u.rm, u.rv
+    stride, pad, training, momentum, eps = u.stride, u.pad, u.training, u.momentum, u.eps
     k, _, r, s = w.shape
     n, h, wd, cx = (x if x is not None else x8[0]).shape  # x None: an fp8-only activation
     count = n * ((h + 2 * pad - r) // stride + 1) * ((wd + 2 * pad - s) // stride + 1)
@@ -871,8 +904,9 @@ def _unit_conv_stats(C, x, w, gamma, beta, rm, rv, stride, pad, training, moment
 class _BnHandoff:
     """What a block leaves on its output tensor so the NEXT block's backward can run this
     block's last BatchNorm backward (relu mask + reduction) inside its own input-gradient
-    dgrad epilogue.  The consumer deposits (g, sums); the producer uses them only if the
-    gradient it receives IS that g (same storage: no other consumer added to it)."""
+    dgrad epilogue.  The consumer (next block) ``offer``s what that epilogue produced; the
+    producer (this block) ``claim``s it, and gets it only if the gradient it receives IS the
+    offered one (same storage: no other consumer added to it)."""
 
     __slots__ = ("y", "stats", "gamma", "beta", "zmask", "deposit", "ds")
 
@@ -882,6 +916,224 @@ class _BnHandoff:
         # gradient g, so the consumer's epilogue reduces it too (kernels.h BnBwdFuse::y2)
         self.ds = ds
         self.deposit = None
+
+    def offer(self, g, sums, dest, acc2):
+        """Consumer: the masked gradient g of this BN's output, its backward ``sums`` (already sent to
+        ``dest``, the _bn_dest of gamma / beta) and the accumulator ``acc2`` of the shortcut BN's, if taken."""
+        self.deposit = (g, sums, dest, acc2)
+
+    def claim(self, dz):
+        """Producer, with the output gradient ``dz`` it received: (sums, dest, shortcut sums) of the offer
+        when dz is the offered g; else all None, after taking an offer back (another consumer contributed)."""
+        if self.deposit is None:
+            return None, None, None
+        g, sums, dest, acc2 = self.deposit
+        self.deposit = None
+        if g.data_ptr() == dz.data_ptr() and g.shape == dz.shape:
+            return sums, dest, acc2
+        if acc2 is not None:
+            acc2.zero_()
+        acc, sg, sb = dest
+        if acc is not None:  # discard the unused sums
+            acc.zero_()
+        else:  # undo the deposited BN-parameter gradients
+            with torch.no_grad():
+                sg.sub_(sums[1] * self.stats[1])
+                sb.sub_(sums[0])
+        return None, None, None
+
+
+class _BlockBackward:
+    """One backward pass of a residual block: its state and its steps.  ``grads``: what autograd gets
+    back per forward tensor; ``sunk``: the parameters whose gradient went in place into the flat buffer
+    instead (``mark_ready`` at the end); ``deferred``: unit -> (accumulator, dgamma sink, dbeta sink) of
+    a BN whose sums sit in an atomic accumulator (its apply adds dgamma / dbeta, its wgrad re-zeroes)."""
+
+    __slots__ = ("C", "det", "side", "grads", "sunk", "deferred", "fp8b", "needs_dx")
+
+    def __init__(self, C, side, ngrads, fp8b, needs_dx):
+        self.C, self.side, self.fp8b, self.needs_dx = C, side, fp8b, needs_dx
+        self.det = deterministic()
+        self.grads = [None] * ngrads
+        self.sunk = []
+        self.deferred = {}
+
+    def bn_finish(self, u, dest, sums):
+        """Unit u's BN backward ``sums`` [sum g, sum g*(y - mean)] are taken and went to ``dest`` (_bn_dest):
+        dgamma / dbeta into ``grads`` for autograd, or the parameters into ``sunk`` and, when the sums sit
+        in an accumulator, the unit into ``deferred`` (its apply adds dgamma / dbeta)."""
+        if dest is None:
+            self.grads[u.base + 1], self.grads[u.base + 2] = sums[1] * u.stats[1], sums[0]
+            return
+        self.sunk += [u.p_gamma, u.p_beta]
+        if dest[0] is not None:
+            self.deferred[u] = dest
+
+    def bn_reduce(self, u, dz, z, mask):
+        """BN backward reduction of unit u as a pass of its own -> sums."""
+        dest = _bn_dest(u.p_gamma, u.p_beta, False)
+        sums = self.C.bn_act_bwd_reduce(dz, z, u.y, u.stats, mask, *(dest[1:] if dest is not None else ()))
+        self.bn_finish(u, dest, sums)
+        return sums
+
+    def apply(self, u, dz, z, sums, mask, want_dres, need_dgrad):
+        """BN backward apply of unit u -> (dy, dres, d8); d8 = (e5m2 dy, its dequant factor)
+        when the dgrad consuming dy runs on fp8 (_fp8_dgrad_ok for the conv's stride), or the
+        weight gradient does (K % 64 == 0 and the conv input's e4m3 copy u.x8 exists)"""
+        C = self.C
+        dfr = self.deferred.get(u)
+        pg = dfr[1:] if dfr is not None else (None, None)
+        if self.fp8b and u.training:
+            k, cin, x8 = dz.shape[3], u.w.shape[1], u.x8
+            wgrad8 = x8 is not None and not self.det and k % 64 == 0 and cin % 16 == 0 and x8[0].shape[3] == cin
+            dgrad8 = _fp8_dgrad_ok(k, u.stride)
+            if (need_dgrad and dgrad8) or wgrad8:
+                stq = _q8_state(u.p_gamma, dz.device, "_pdt_q8b")
+                slot = stq.next_slot()
+                # fp8-only dy: the dgrad (if any) and the weight gradient both read the e5m2 copy
+                want_dy = not (_FP8_ONLY and wgrad8 and (not need_dgrad or dgrad8))
+                dy, dres, q = C.bn_act_bwd_apply_q8(dz, z, u.y, u.stats, u.gamma, sums, mask, want_dres,
+                                                    stq.buf, slot, want_dy, *pg)
+                return dy, dres, (q, stq.deq(slot))
+        dy, dres = C.bn_act_bwd_apply(dz, z, u.y, u.stats, u.gamma, sums, mask, u.training, want_dres, *pg)
+        return dy, dres, None
+
+    def wgrad(self, u, dy, xin, d8):
+        """Weight gradient of unit u from dy (bf16) / d8 (e5m2) and its conv input xin / u.x8, and the
+        re-zero of the unit's BN-sum accumulator behind it (its apply is queued)."""
+        C, side, w, x8 = self.C, self.side, u.w, u.x8
+        sink = _grad_sink(u.p_w)
+        dfr = self.deferred.pop(u, None)
+        zero = dfr[0] if dfr is not None else None
+        k, c = w.shape[0], w.shape[1]
+        if d8 is not None and x8 is not None and not self.det and c % 16 == 0 and k % 64 == 0 and x8[0].shape[3] == c:
+            # e5m2 dy x e4m3 x on the MX-rate MFMA, both already produced for the fp8 GEMMs
+            dw = C.conv_wgrad_fp8(side.cuda_stream if sink is not None and side is not None else 0, d8[0], x8[0],
+                                  d8[1], x8[1], list(w.shape), u.stride, u.pad, sink, zero)
+            if sink is not None:
+                self.sunk.append(u.p_w)
+            else:
+                self.grads[u.base] = dw.to(w.dtype)
+            return
+        if dy is None or xin is None:
+            raise RuntimeError("fp8-only operands reached the bf16 weight gradient")
+        if sink is not None and side is not None:
+            # into the flat buffer on the side stream, concurrent with the dgrad chain; all-reduce and optimizer
+            # wait for that stream (streams.py).  One native call: stream hand-off, launch, record_stream, re-zero
+            C.conv_wgrad_side(side.cuda_stream, dy, xin, list(w.shape), u.stride, u.pad, self.det, sink, zero)
+            self.sunk.append(u.p_w)
+            return
+        self.grads[u.base] = _wgrad_into(u.p_w, self.sunk, C.conv_wgrad, dy, xin, list(w.shape), u.stride, u.pad,
+                                         self.det)
+        if zero is not None:
+            zero.zero_()
+
+    def dgrad(self, u, dy, d8, xshape, stride, pad, addend):
+        """Input gradient of unit u's conv (``addend`` summed in its epilogue)."""
+        C = self.C
+        if d8 is not None and _fp8_dgrad_ok(d8[0].shape[3], stride):
+            wt8, wsc = _packed_crsk8(C, u.w)
+            return C.conv_dgrad_fp8(d8[0], wt8, wsc, d8[1], xshape, stride, pad, addend)
+        return C.conv_dgrad(dy, u.w, xshape, stride, pad, addend, _packed_crsk(u.w))
+
+    def dgrad_bn(self, u, dy, d8, xshape, addend, y, z, stats, mask, dest, bn2=None):
+        """Input gradient of unit u's conv with, in its epilogue, the backward (ReLU mask ``mask`` from
+        ``z``, reduction) of the BN (y, stats) that produced the conv's input -> (g, sums), the sums going
+        to ``dest`` (_bn_dest).  bn2 = (y2, stats2, acc2): a second BN of the same gradient (bf16 only)."""
+        C = self.C
+        acc, sg, sb = dest if dest is not None else (None, None, None)
+        if acc is not None:
+            sg = sb = None  # the sums stay in acc: the BN's apply adds dgamma / dbeta into the sinks
+        if d8 is not None and _fp8_dgrad_ok(d8[0].shape[3], u.stride):
+            assert bn2 is None
+            wt8, wsc = _packed_crsk8(C, u.w)
+            return C.conv_dgrad_bn_fp8(d8[0], wt8, wsc, d8[1], xshape, u.stride, u.pad, addend, y, z, stats, mask,
+                                       sg, sb, acc)
+        return C.conv_dgrad_bn(dy, u.w, xshape, u.stride, u.pad, addend, y, z, stats, mask, sg, sb,
+                               _packed_crsk(u.w), acc, *(bn2 if bn2 is not None else ()))
+
+    def dgrad_handoff(self, u, dy, d8, x, addend, hi):
+        """The block's input gradient (first unit u; ``addend`` = the shortcut's gradient).  With a
+        hand-off ``hi`` whose BN has gradient sinks, the previous block's last BN backward runs in the
+        epilogue (ReLU mask from its output z = x) and is offered to that block."""
+        dest = _bn_dest(hi.gamma, hi.beta, _BN_ACC and not self.det) if hi is not None else None
+        if dest is None:
+            return self.dgrad(u, dy, d8, list(x.shape), u.stride, u.pad, addend)
+        zsrc, zmode = (hi.zmask, 3) if hi.zmask is not None else (x, 1)
+        bn2 = None
+        ds = hi.ds  # the previous block's projection-shortcut BN, reduced in the same epilogue
+        if (dest[0] is not None and ds is not None and zmode == 3 and addend is not None
+                and (d8 is None or not _fp8_dgrad_ok(d8[0].shape[3], u.stride)) and _grad_sink(ds[2]) is not None):
+            bn2 = (ds[0], ds[1], _bacc(ds[2], hi.stats.shape[1]))
+        dz, sums = self.dgrad_bn(u, dy, d8, list(x.shape), addend, hi.y, zsrc, hi.stats, zmode, dest, bn2)
+        hi.offer(dz, sums, dest, bn2[2] if bn2 is not None else None)
+        return dz
+
+    def fold(self, u, g, sums, xin, colsum):
+        """BN backward of the last unit u folded into its input gradient (kernels.h DgradFold) -> the
+        folded weights: the dgrad reads [g | x] against [w*k1 | W^T diag(a) W] + bias instead of the
+        applied dy, and the weight gradient needs no dy either: dW = diag(k1) g^T x + diag(a) W x^T x +
+        b sum(x), on the side stream (also the BN parameter gradients and the accumulator re-zero).
+        ``colsum``: the forward's sum_m x ([S, C] atomic slots, or deterministic [C] sums) or None."""
+        global FOLD_CALLS
+        FOLD_CALLS += 1
+        C, side, w, stats = self.C, self.side, u.w, u.stats
+        wt = _packed_crsk(w)
+        if wt is None:
+            wt = C.pack_weight_t(w)
+        k, c = w.shape[0], w.shape[1]
+        count = u.y.numel() // k
+        fold = C.bn_fold_weights(wt.view(c, k), stats, u.gamma, sums, count)
+        streams.fork(side, g, stats, sums, wt, xin)
+        with torch.cuda.stream(side):
+            # T1 and Gram accumulate into persistent zeroed workspaces that bn_fold_wgrad
+            # clears after reading (with the consumed BN-sum accumulator): no memset / fill
+            t1, gram, done = _fold_ws(k, c, xin.device)
+            C.conv_wgrad(g, xin, [k, c, 1, 1], 1, 0, self.det, t1)
+            C.conv_wgrad(xin, xin, [c, c, 1, 1], 1, 0, self.det, gram)
+            if colsum is None:
+                colsum = C.bn_act_bwd_reduce(xin, xin, xin, _zero_stats(c, xin.device), 0)[0]
+            dfr = self.deferred.pop(u, None)
+            _, sg, sb = dfr if dfr is not None else (None, None, None)
+            C.bn_fold_wgrad(t1, gram, colsum, wt.view(c, k), stats, u.gamma, sums, count, _grad_sink(u.p_w),
+                            sg, sb, done, dfr is not None)
+        self.sunk.append(u.p_w)
+        return fold
+
+    def dgrad_bn_fold(self, prev, g, xin, fold):
+        """The folded input gradient with unit ``prev``'s BN backward in its epilogue -> (g, sums): into the
+        atomic accumulator, or (deterministic) fixed-order partials + reduce straight into the sinks."""
+        dest = _bn_dest(prev.p_gamma, prev.p_beta, not self.det)
+        pre = self.C.conv_dgrad_bn_fold(g, xin, fold[0], fold[1], prev.y, None, prev.stats, 2,
+                                        *(dest[:1] if dest[0] is not None else dest))
+        self.bn_finish(prev, dest, pre[1])
+        return pre
+
+    def shortcut(self, s, g_short, x, sums_dep):
+        """Projection shortcut s: BN backward (reduce + apply), weight gradient, and the input
+        gradient that the first conv's dgrad epilogue adds (None when x needs none).  ``sums_dep``:
+        the BN's backward sums when the next block's hand-off epilogue took them."""
+        if sums_dep is not None:
+            # the apply adds dgamma / dbeta and the weight gradient re-zeroes the accumulator (as for
+            # every acc-mode BN)
+            global DUAL_CALLS
+            DUAL_CALLS += 1
+            sums = sums_dep
+            self.bn_finish(s, (sums, _grad_sink(s.p_gamma), _grad_sink(s.p_beta)), sums)
+        else:
+            sums = self.bn_reduce(s, g_short, g_short, 0)
+        dy, _, d8 = self.apply(s, g_short, g_short, sums, 0, False, self.needs_dx)
+        self.wgrad(s, dy, x, d8)
+        if not self.needs_dx:
+            return None
+        if s.stride == 2 and s.pad == 0 and s.w.shape[2] == 1 and s.w.shape[3] == 1:
+            # 1x1/s2 shortcut: its input gradient is zero at every odd (h, w), so it is
+            # computed as a dense 1x1 dgrad on the stride-2 grid and the first conv's
+            # dgrad epilogue adds it at even positions only (no full-resolution tensor,
+            # no all-zero parity-class launches)
+            n, h, w, c = x.shape
+            return self.dgrad(s, dy, d8, [n, (h + 1) // 2, (w + 1) // 2, c], 1, 0, None)
+        return self.dgrad(s, dy, d8, list(x.shape), s.stride, s.pad, None)
 
 
 class _ResidualBlock(torch.autograd.Function):
@@ -895,66 +1147,60 @@ class _ResidualBlock(torch.autograd.Function):
     ``_BnHandoff`` -- the previous block's last unit; the remaining per-unit pass is
     one elementwise apply.
     tensors = per unit (w, gamma, beta, running_mean, running_var), chain units
-    first, then the downsample unit if present.
+    first, then the downsample unit if present (``_block_units``).
     """
 
     @staticmethod
     def forward(ctx, x, spec, handoff, fp8io, *tensors):
         C = native()
-        _nan_trace(f"block-in {tuple(x.shape)}", x=x)
+        if _NAN_TRACE:
+            _nan_trace(f"block-in {tuple(x.shape)}", x=x)
         if _LEAD is not None:
             _lead_mark(f"fwd {tuple(x.shape)}")
-        chain, ds_cfg, spec_tail = spec
-        nch = len(chain)
-        saved = [x]
+        units, shortcut = _block_units(spec, tensors)
+        nch = len(units)
         # fp8io = (x8, per-chain-unit _Q8State list, holder for the output's e4m3 copy) or None
         x8, q8s, holder = fp8io if fp8io is not None else (None, None, None)
         # shortcut first (it only needs x) so its output can be freed into the tail's add
         ds_join = None
-        if ds_cfg is not None:
-            w, g, b, rm, rv = tensors[5 * nch:5 * nch + 5]
-            st, pd, tr, mo, ep = ds_cfg
+        if shortcut is None:
+            res = x
+        elif q8s is not None:  # fp8: the tail's apply takes a materialised residual
+            res, y_ds, st_ds, _, _ = _unit_fwd(C, x, shortcut, False, None, x8)
+        else:
+            # projection shortcut: conv + statistics only; its BN apply runs inside the block
+            # tail's apply pass (bn_act_fwd RESBN), so the normalised shortcut is never stored
             br = streams.branch_stream(x.device) if x.is_cuda and nch > 1 else None
-            if q8s is None and _FUSE_RES_BN and br is not None:
-                # projection shortcut on the branch stream, concurrent with the chain's first
-                # units; the tail unit (which applies its BN inside the residual add) waits
+            if br is not None:
+                # on the branch stream, concurrent with the chain's first units; the tail unit waits
                 buffers_ready()  # a deferred BN-buffer wait lands on this stream, before the fork
                 main = streams.fork(br, x)
                 with torch.cuda.stream(br):
-                    y_ds, st_ds = _unit_conv_stats(C, x, w, g, b, rm, rv, st, pd, tr, mo, ep, x8)
+                    y_ds, st_ds = _unit_conv_stats(C, x, shortcut, x8)
                 ds_join = (main, streams.join(br, main, y_ds, st_ds))
-                res = (y_ds, st_ds)
-            elif q8s is None and _FUSE_RES_BN:
-                # projection shortcut: conv + statistics only; its BN apply runs inside the block
-                # tail's apply pass (bn_act_fwd RESBN), so the normalised shortcut is never stored
-                y_ds, st_ds = _unit_conv_stats(C, x, w, g, b, rm, rv, st, pd, tr, mo, ep, x8)
-                res = (y_ds, st_ds)
             else:
-                res, y_ds, st_ds, _, _ = _unit_fwd(C, x, w, g, b, rm, rv, st, pd, False, tr, mo, ep, None, x8)
-        else:
-            res = x
+                y_ds, st_ds = _unit_conv_stats(C, x, shortcut, x8)
+            res = (y_ds, st_ds)
         h, h8 = x, x8
         outs = []
         ins8 = [x8]  # e4m3 copy (q, dequant factor) of each chain unit's conv input, or None
         zmask = None
         # the last unit's folded weight gradient needs sum_m of its conv input: summed by the apply
         # that writes that input (no reduction pass in backward)
-        fold_fwd = not spec_tail and fp8io is None and _fold_colsum_ok(chain, tensors, x)
+        fold_fwd = not spec[2] and fp8io is None and _fold_colsum_ok(units, x)
         det_fwd = deterministic()
-        csum = _csum_slots(tensors[5 * (nch - 1)], x.device) if fold_fwd and not det_fwd else None
+        csum = _csum_slots(units[-1].w, x.device) if fold_fwd and not det_fwd else None
         ctx.colsum = csum
-        for i, (st, pd, tr, mo, ep) in enumerate(chain):
-            w, g, b, rm, rv = tensors[5 * i:5 * i + 5]
+        for i, u in enumerate(units):
             last = i == nch - 1
             if last and ds_join is not None:
                 ds_join[0].wait_event(ds_join[1])
-            # the block output's ReLU mask as bits: the next block's BN-fused dgrad reads it
-            # instead of z (1/16 of the bytes)
-            want_z = last or q8s is None or not _fp8_only_ok(tensors[5 * (i + 1)], w.shape[0], tr)
-            z, y, stt, h8, zm = _unit_fwd(C, h, w, g, b, rm, rv, st, pd, True, tr, mo, ep,
-                                          res if last else None, h8, q8s[i] if q8s else None,
-                                          want_mask=last and tr and _ZMASK and _BN_HANDOFF and _FUSE_DGRAD_BN,
-                                          want_z=want_z, csum=csum if i == nch - 2 else None)
+            want_z = last or q8s is None or not _fp8_only_ok(units[i + 1].w, u.w.shape[0], u.training)
+            # want_mask: the block output's ReLU mask as bits -- the next block's BN-fused dgrad
+            # reads it instead of z (1/16 of the bytes)
+            z, y, stt, h8, zm = _unit_fwd(C, h, u, True, res if last else None, h8, q8s[i] if q8s else None,
+                                          want_mask=last and u.training, want_z=want_z,
+                                          csum=csum if i == nch - 2 else None)
             if z is None and h8 is None:
                 raise RuntimeError("fp8-only activation without its e4m3 copy")
             if fold_fwd and det_fwd and i == nch - 2:
@@ -969,28 +1215,26 @@ class _ResidualBlock(torch.autograd.Function):
                 zmask = zm
             else:
                 ins8.append(h8)
-            outs.append((z, y, stt))
+            outs += [z, y, stt]
             h = z
         if holder is not None and h8 is not None:
             holder.append(h8)
         if _CAPTURE is not None:
-            _CAPTURE.append([z for z, _, _ in outs])
-        for ui, (z, y, stt) in enumerate(outs):
-            saved += [z, y, stt]
-            _nan_trace(f"fwd block{id(ctx) % 10007} unit{ui} {tuple(y.shape)}", z=z, y=y, stats=stt)
-        if ds_cfg is not None:
-            saved += [y_ds, st_ds]
-        ctx.save_for_backward(*saved, *tensors)
+            _CAPTURE.append(outs[0::3])
+        if _NAN_TRACE:
+            for ui in range(nch):
+                _nan_trace(f"fwd block{id(ctx) % 10007} unit{ui}", z=outs[3 * ui], y=outs[3 * ui + 1],
+                           stats=outs[3 * ui + 2])
+        if shortcut is not None:
+            outs += [y_ds, st_ds]
+        ctx.save_for_backward(x, *outs, *tensors)  # the layout _block_units reads back
         ctx.params = tensors  # the Parameter objects: gradients may be written into flat views
         ctx.spec = spec
-        ctx.ntensors = len(tensors)
         ctx.handoff_in = handoff  # the producer of x (previous block), or None
         ctx.fp8b = fp8io is not None and _FP8_BWD  # fp8 dgrads in backward (dy in e5m2)
         ctx.in8 = ins8 if ctx.fp8b and _FP8_WGRAD else None  # fp8 weight-gradient operands
-        _, y_last, st_last = outs[-1]
-        ctx.handoff_out = _BnHandoff(y_last, st_last, tensors[5 * (nch - 1) + 1],
-                                     tensors[5 * (nch - 1) + 2], zmask,
-                                     (y_ds, st_ds, tensors[5 * nch + 1]) if ds_cfg is not None and _DUAL_BN else None)
+        ctx.handoff_out = _BnHandoff(y, stt, u.gamma, u.beta, zmask,  # y, stt, u: the last unit's
+                                     (y_ds, st_ds, shortcut.gamma) if shortcut is not None and _DUAL_BN else None)
         return h
 
     @staticmethod
@@ -998,361 +1242,121 @@ class _ResidualBlock(torch.autograd.Function):
         C = native()
         if _LEAD is not None:
             _lead_mark(f"bwd {tuple(dz.shape)}")
-        chain, ds_cfg, _ = ctx.spec
-        nch = len(chain)
         sv = ctx.saved_tensors
         x = sv[0]
-        units = [sv[1 + 3 * i:4 + 3 * i] for i in range(nch)]
-        pos = 1 + 3 * nch
-        if ds_cfg is not None:
-            y_ds, st_ds = sv[pos:pos + 2]
-            pos += 2
-        tensors = sv[pos:]
-        if _NAN_TRACE:
-            for ui, (z_, y_, s_) in enumerate(units):
-                _nan_trace(f"bwd-entry block{id(ctx) % 10007} unit{ui} {tuple(y_.shape)}", z=z_, y=y_, stats=s_)
-            _nan_trace(f"bwd-entry block{id(ctx) % 10007} dz", dz=dz)
-        grads = [None] * ctx.ntensors
-        dz = dz.contiguous()
-        det = deterministic()
-        g_short = None
-        params = ctx.params
-        sunk = []  # parameters whose gradient was accumulated in place into the flat buffer
-
-        side = streams.begin(x.device)
-
-        in8 = ctx.in8
+        units, shortcut = _block_units(ctx.spec, ctx.params, sv, ctx.in8)
         ctx.in8 = None
-
-        deferred = {}  # unit j -> (accumulator, dgamma sink, dbeta sink): BN sums from epilogue atomics
-
-        def wgrad(j, dy_, xin_, st_, pd_, d8_=None, x8_=None):
-            w_ = tensors[j]
-            sink = _grad_sink(params[j])
-            dfr = deferred.pop(j, None)
-            zero = dfr[0] if dfr is not None else None  # its apply is queued: re-zero on the side stream
-            k_, c_ = w_.shape[0], w_.shape[1]
-            if (d8_ is not None and x8_ is not None and not det and c_ % 16 == 0 and k_ % 64 == 0
-                    and x8_[0].shape[3] == c_):
-                # e5m2 dy x e4m3 x on the MX-rate MFMA, both already produced for the fp8 GEMMs
-                if sink is not None:
-                    C.conv_wgrad_fp8(side.cuda_stream if side is not None else 0, d8_[0], x8_[0], d8_[1],
-                                     x8_[1], list(w_.shape), st_, pd_, sink, zero)
-                    sunk.append(params[j])
-                else:
-                    grads[j] = C.conv_wgrad_fp8(0, d8_[0], x8_[0], d8_[1], x8_[1], list(w_.shape), st_,
-                                                pd_, None, zero).to(w_.dtype)
-                return
-            if dy_ is None or xin_ is None:
-                raise RuntimeError("fp8-only operands reached the bf16 weight gradient")
-            if sink is not None:
-                # weight gradient into the flat buffer on the side stream, concurrent with the
-                # dgrad chain; all-reduce and optimizer wait for that stream (streams.py)
-                if side is not None:  # one native call: stream hand-off, launch, record_stream
-                    C.conv_wgrad_side(side.cuda_stream, dy_, xin_, list(w_.shape), st_, pd_, det, sink, zero)
-                    zero = None
-                else:
-                    C.conv_wgrad(dy_, xin_, list(w_.shape), st_, pd_, det, sink)
-                sunk.append(params[j])
-            else:
-                grads[j] = C.conv_wgrad(dy_, xin_, list(w_.shape), st_, pd_, det).to(w_.dtype)
-            if zero is not None:
-                zero.zero_()
-
-        def bnreduce(j, dz_, z_, y_, stt_, mask_):
-            if z_ is None:  # fp8-only z: interior units recompute the ReLU mask from y (mask 2)
-                assert mask_ != 1
-                z_ = y_
-            sg, sb = _grad_sink(params[j + 1]), _grad_sink(params[j + 2])
-            if sg is not None and sb is not None:
-                sums_ = C.bn_act_bwd_reduce(dz_, z_, y_, stt_, mask_, sg, sb)
-                sunk.extend([params[j + 1], params[j + 2]])
-            else:
-                sums_ = C.bn_act_bwd_reduce(dz_, z_, y_, stt_, mask_)
-                grads[j + 1] = sums_[1] * stt_[1]
-                grads[j + 2] = sums_[0]
-            return sums_
-
-        def apply(j, dz_, z_, y_, stt_, sums_, mask_, tr_, want_dres, need_dgrad, x8_=None, stride_=0):
-            """BN backward apply of unit j -> (dy, dres, d8); d8 = (e5m2 dy, its dequant factor)
-            when the dgrad consuming dy runs on fp8 (_fp8_dgrad_ok for the conv's stride), or the
-            weight gradient does (K % 64 == 0 and the conv input's e4m3 copy x8_ exists)"""
-            gamma_ = tensors[j + 1]
-            k_ = dz_.shape[3]
-            dfr = deferred.get(j)
-            pg = (dfr[1], dfr[2]) if dfr is not None else (None, None)
-            wgrad8 = (x8_ is not None and not det and k_ % 64 == 0 and tensors[j].shape[1] % 16 == 0
-                      and x8_[0].shape[3] == tensors[j].shape[1])
-            dgrad8 = _fp8_dgrad_ok(k_, stride_)
-            if ctx.fp8b and tr_ and ((need_dgrad and dgrad8) or wgrad8):
-                stq = _q8_state(params[j + 1], dz_.device, "_pdt_q8b")
-                slot = stq.next_slot()
-                # fp8-only dy: the dgrad (if any) and the weight gradient both read the e5m2 copy
-                want_dy = not (_FP8_ONLY and wgrad8 and (not need_dgrad or dgrad8))
-                dy_, dres_, q_ = C.bn_act_bwd_apply_q8(dz_, z_ if z_ is not None else y_, y_, stt_, gamma_,
-                                                       sums_, mask_, want_dres, stq.buf, slot, want_dy, *pg)
-                return dy_, dres_, (q_, stq.deq(slot))
-            dy_, dres_ = C.bn_act_bwd_apply(dz_, z_ if z_ is not None else y_, y_, stt_, gamma_, sums_, mask_,
-                                            tr_, want_dres, *pg)
-            return dy_, dres_, None
-
-        def dgrad(dy_, d8_, w_, xshape, st_, pd_, addend_):
-            if d8_ is not None and _fp8_dgrad_ok(d8_[0].shape[3], st_):
-                wt8, wsc = _packed_crsk8(C, w_)
-                return C.conv_dgrad_fp8(d8_[0], wt8, wsc, d8_[1], xshape, st_, pd_, addend_)
-            return C.conv_dgrad(dy_, w_, xshape, st_, pd_, addend_, _packed_crsk(w_))
-
-        def dgrad_bn_any(dy_, d8_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_, sg=None, sb=None, acc=None,
-                         bn2=None):
-            if d8_ is not None and _fp8_dgrad_ok(d8_[0].shape[3], st_):
-                assert bn2 is None
-                wt8, wsc = _packed_crsk8(C, w_)
-                return C.conv_dgrad_bn_fp8(d8_[0], wt8, wsc, d8_[1], xshape, st_, pd_, addend_, y_, z_,
-                                           stt_, mask_, sg, sb, acc)
-            if bn2 is not None:
-                return C.conv_dgrad_bn(dy_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_, sg, sb,
-                                       _packed_crsk(w_), acc, bn2[0], bn2[1], bn2[2])
-            return C.conv_dgrad_bn(dy_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_, sg, sb,
-                                   _packed_crsk(w_), acc)
-
-        def dgrad_bn(j, dy_, d8_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_):
-            """input gradient of a conv + BN backward reduction of unit j (its producer)"""
-            sg, sb = _grad_sink(params[j + 1]), _grad_sink(params[j + 2])
-            if sg is not None and sb is not None and _BN_ACC and not det:
-                acc = _bacc(params[j + 1], stt_.shape[1])
-                g_, sums_ = dgrad_bn_any(dy_, d8_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_, acc=acc)
-                deferred[j] = (acc, sg, sb)  # the apply of unit j adds dgamma / dbeta
-                sunk.extend([params[j + 1], params[j + 2]])
-            elif sg is not None and sb is not None:
-                g_, sums_ = dgrad_bn_any(dy_, d8_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_, sg, sb)
-                sunk.extend([params[j + 1], params[j + 2]])
-            else:
-                g_, sums_ = dgrad_bn_any(dy_, d8_, w_, xshape, st_, pd_, addend_, y_, z_, stt_, mask_)
-                grads[j + 1] = sums_[1] * stt_[1]
-                grads[j + 2] = sums_[0]
-            return g_, sums_
-
-        def shortcut_backward(g_short_):
-            """projection shortcut: BN backward (reduce + apply), weight gradient, and the input
-            gradient that the first conv's dgrad epilogue adds (None when x needs none)"""
-            st2, pd2, tr2, _, _ = ds_cfg
-            wds = tensors[5 * nch]
-            if sums_ds_dep is not None:
-                # reduced by the next block's hand-off epilogue: the apply adds dgamma / dbeta and the
-                # weight gradient re-zeroes the accumulator (as for every acc-mode BN)
-                global DUAL_CALLS
-                DUAL_CALLS += 1
-                sums_ds = sums_ds_dep
-                deferred[5 * nch] = (sums_ds, _grad_sink(params[5 * nch + 1]), _grad_sink(params[5 * nch + 2]))
-                sunk.extend([params[5 * nch + 1], params[5 * nch + 2]])
-            else:
-                sums_ds = bnreduce(5 * nch, g_short_, g_short_, y_ds, st_ds, 0)
-            dy_ds, _, d8_ds = apply(5 * nch, g_short_, g_short_, y_ds, st_ds, sums_ds, 0, tr2, False,
-                                    ctx.needs_input_grad[0], in8[0] if in8 else None, st2)
-            wgrad(5 * nch, dy_ds, x, st2, pd2, d8_ds, in8[0] if in8 else None)
-            if not ctx.needs_input_grad[0]:
-                return None
-            if st2 == 2 and pd2 == 0 and wds.shape[2] == 1 and wds.shape[3] == 1 and _COMPACT_ADDEND:
-                # 1x1/s2 shortcut: its input gradient is zero at every odd (h, w), so it is
-                # computed as a dense 1x1 dgrad on the stride-2 grid and the first conv's
-                # dgrad epilogue adds it at even positions only (no full-resolution tensor,
-                # no all-zero parity-class launches)
-                n_, h_, w_, c_ = x.shape
-                return dgrad(dy_ds, d8_ds, wds, [n_, (h_ + 1) // 2, (w_ + 1) // 2, c_], 1, 0, None)
-            return dgrad(dy_ds, d8_ds, wds, list(x.shape), st2, pd2, None)
-
-        ds_br = streams.branch_stream(x.device) if ds_cfg is not None and x.is_cuda else None
+        nch = len(units)
+        if _NAN_TRACE:
+            for ui, u in enumerate(units):
+                _nan_trace(f"bwd-entry block{id(ctx) % 10007} unit{ui} {tuple(u.y.shape)}", z=u.z, y=u.y, stats=u.stats)
+            _nan_trace(f"bwd-entry block{id(ctx) % 10007} dz", dz=dz)
+        dz = dz.contiguous()
+        bw = _BlockBackward(C, streams.begin(x.device), len(ctx.params), ctx.fp8b, ctx.needs_input_grad[0])
+        ds_br = streams.branch_stream(x.device) if shortcut is not None and x.is_cuda else None
         ds_join = None
 
-        # gradient arriving pre-masked and pre-reduced from the next block's dgrad epilogue?
-        pre = None
-        ho = ctx.handoff_out
-        sums_ds_dep = None  # the shortcut BN's (sum g, sum g*(y_ds - mean)) from the same epilogue
-        if ho.deposit is not None:
-            g_dep, sums_dep, acc_dep, acc2_dep = ho.deposit
-            ho.deposit = None
-            if acc2_dep is not None:
-                if g_dep.data_ptr() == dz.data_ptr() and g_dep.shape == dz.shape:
-                    sums_ds_dep = acc2_dep
-                else:
-                    acc2_dep.zero_()
-            jl = 5 * (nch - 1)
-            if g_dep.data_ptr() == dz.data_ptr() and g_dep.shape == dz.shape:
-                pre = (dz, sums_dep)
-                sunk.extend([params[jl + 1], params[jl + 2]])
-                if acc_dep is not None:  # atomic sums: this block's apply adds dgamma / dbeta
-                    deferred[jl] = (acc_dep, _grad_sink(params[jl + 1]), _grad_sink(params[jl + 2]))
-            elif acc_dep is not None:  # another consumer contributed: discard the unused sums
-                acc_dep.zero_()
-            else:  # another consumer contributed: undo the deposited BN-parameter gradients
-                inv = units[nch - 1][2][1]
-                with torch.no_grad():
-                    _grad_sink(params[jl + 1]).sub_(sums_dep[1] * inv)
-                    _grad_sink(params[jl + 2]).sub_(sums_dep[0])
+        # does the gradient arrive masked and reduced from the next block's dgrad epilogue?  sums_ds: the
+        # shortcut BN's (sum g, sum g*(y_ds - mean)) from the same epilogue
+        sums, dest, sums_ds = ctx.handoff_out.claim(dz)
         ctx.handoff_out = None
+        pre = None  # (g = dz * relu'(unit), the unit's BN backward sums of g)
+        if sums is not None:
+            pre = (dz, sums)
+            bw.bn_finish(units[-1], dest, sums)
 
         for i in reversed(range(nch)):
-            st, pd, tr, mo, ep = chain[i]
-            z, y, stt = units[i]
-            w, gamma = tensors[5 * i], tensors[5 * i + 1]
-            xin = x if i == 0 else units[i - 1][0]  # None: fp8-only (its e4m3 copy is in8[i])
-            xin_shape = list((xin if xin is not None else units[i - 1][1]).shape)
+            u = units[i]
             last = i == nch - 1
-            need_dx = i > 0 or ctx.needs_input_grad[0]
-            if pre is None:
-                mask = 1 if last else 2  # inner units: ReLU mask recomputed from y, z never read
-                sums = bnreduce(5 * i, dz, z, y, stt, mask)
-                dy, dres, d8 = apply(5 * i, dz, z, y, stt, sums, mask, tr, last, need_dx, in8[i] if in8 else None,
-                                     st)
-            else:
-                g, sums = pre  # g = dz * relu'(unit i), reduced in the producing epilogue
-                dres = g
+            xin = x if i == 0 else units[i - 1].z  # None: fp8-only (its e4m3 copy is u.x8)
+            need_dx = i > 0 or bw.needs_dx
             fold = None
-            if pre is not None and _fold_ok(i, last, w, xin, st, pd, tr, det, side, ctx.fp8b, params):
-                # BN backward folded into the input gradient (kernels.h DgradFold): the dgrad below
-                # reads [g | x] against [w*k1 | W^T diag(a) W] + bias instead of the applied dy, so the
-                # apply -- now feeding only the weight gradient -- runs on the side stream with it
-                wt = _packed_crsk(w)
-                if wt is None:
-                    wt = C.pack_weight_t(w)
-                global FOLD_CALLS
-                FOLD_CALLS += 1
-                k_, c_ = w.shape[0], w.shape[1]
-                count = y.numel() // k_
-                fold = C.bn_fold_weights(wt.view(c_, k_), stt, gamma, sums, count)
-                # the weight gradient without dy either: dW = diag(k1) g^T x + diag(a) W x^T x + b sum(x),
-                # on the side stream (also the BN parameter gradients and the accumulator re-zero)
-                streams.fork(side, g, stt, sums, wt, xin)
-                with torch.cuda.stream(side):
-                    # T1 and Gram accumulate into persistent zeroed workspaces that bn_fold_wgrad
-                    # clears after reading (with the consumed BN-sum accumulator): no memset / fill
-                    t1, gram, done = _fold_ws(k_, c_, xin.device)
-                    C.conv_wgrad(g, xin, [k_, c_, 1, 1], 1, 0, det, t1)
-                    C.conv_wgrad(xin, xin, [c_, c_, 1, 1], 1, 0, det, gram)
-                    colsum = ctx.colsum  # forward: [S, C] atomic slots, or (deterministic) [C] sums
-                    if colsum is None:
-                        colsum = C.bn_act_bwd_reduce(xin, xin, xin, _zero_stats(c_, xin.device), 0)[0]
-                    ctx.colsum = None  # consumed: bn_fold_wgrad re-zeroes the [S, C] slots
-                    dfr = deferred.pop(5 * i, None)
-                    C.bn_fold_wgrad(t1, gram, colsum, wt.view(c_, k_), stt, gamma, sums, count,
-                                    _grad_sink(params[5 * i]), dfr[1] if dfr is not None else None,
-                                    dfr[2] if dfr is not None else None, done, dfr is not None)
-                sunk.append(params[5 * i])
-            elif pre is not None:
-                dy, _, d8 = apply(5 * i, g, g, y, stt, sums, 0, tr, False, need_dx, in8[i] if in8 else None, st)
-            pre = None
-            if fold is None:
-                wgrad(5 * i, dy, xin, st, pd, d8, in8[i] if in8 else None)
-            if last:
-                g_short = dres
-                if ds_cfg is not None and nch > 1 and ds_br is not None:
-                    # projection-shortcut backward on the branch stream, concurrent with the
-                    # chain's remaining units; the first conv's dgrad waits for its addend
-                    main = streams.fork(ds_br, g_short, y_ds, st_ds, x)
-                    with torch.cuda.stream(ds_br):
-                        addend_br = shortcut_backward(g_short)
-                    ds_join = (main, streams.join(ds_br, main, addend_br), addend_br)
-            if i > 0:
-                yp, sttp = units[i - 1][1], units[i - 1][2]
-                if fold is not None:
-                    j = 5 * (i - 1)
-                    if det:  # fixed-order partials + reduce; dgamma / dbeta straight into the sinks
-                        pre = C.conv_dgrad_bn_fold(g, xin, fold[0], fold[1], yp, None, sttp, 2, None,
-                                                   _grad_sink(params[j + 1]), _grad_sink(params[j + 2]))
-                    else:
-                        acc = _bacc(params[j + 1], sttp.shape[1])
-                        pre = C.conv_dgrad_bn_fold(g, xin, fold[0], fold[1], yp, None, sttp, 2, acc)
-                        deferred[j] = (acc, _grad_sink(params[j + 1]), _grad_sink(params[j + 2]))
-                    sunk.extend([params[j + 1], params[j + 2]])
-                elif _FUSE_DGRAD_BN:
-                    pre = dgrad_bn(5 * (i - 1), dy, d8, w, xin_shape, st, pd, None, yp, None, sttp, 2)
+            if pre is None:
+                # reduce, then apply.  Only the last unit of a block nothing was handed to gets here:
+                # every other unit's sums come from the epilogue of the dgrad behind it
+                assert last
+                sums = bw.bn_reduce(u, dz, u.z, 1)
+                dy, g_short, d8 = bw.apply(u, dz, u.z, sums, 1, True, need_dx)
+            else:
+                g, sums = pre  # reduced in the producing epilogue
+                if last:
+                    g_short = g
+                if last and i > 0 and _fold_ok(u, units[i - 1], xin, bw):
+                    # the apply -- feeding only the weight gradient -- goes with it to the side stream
+                    colsum, ctx.colsum = ctx.colsum, None  # consumed: bn_fold_wgrad re-zeroes the [S, C] slots
+                    fold = bw.fold(u, g, sums, xin, colsum)
                 else:
-                    dz = dgrad(dy, d8, w, xin_shape, st, pd, None)
+                    dy, _, d8 = bw.apply(u, g, g, sums, 0, False, need_dx)
+            if fold is None:
+                bw.wgrad(u, dy, xin, d8)
+            if last and shortcut is not None and nch > 1 and ds_br is not None:
+                # projection-shortcut backward on the branch stream, concurrent with the
+                # chain's remaining units; the first conv's dgrad waits for its addend
+                main = streams.fork(ds_br, g_short, shortcut.y, shortcut.stats, x)
+                with torch.cuda.stream(ds_br):
+                    addend = bw.shortcut(shortcut, g_short, x, sums_ds)
+                ds_join = (main, streams.join(ds_br, main, addend))
+            if i > 0:
+                prev = units[i - 1]
+                if fold is not None:
+                    pre = bw.dgrad_bn_fold(prev, g, xin, fold)
+                else:
+                    dest = _bn_dest(prev.p_gamma, prev.p_beta, _BN_ACC and not bw.det)
+                    pre = bw.dgrad_bn(u, dy, d8, list((xin if xin is not None else prev.y).shape), None,
+                                      prev.y, None, prev.stats, 2, dest)
+                    bw.bn_finish(prev, dest, pre[1])
             else:
                 # shortcut gradient: identity -> g_short itself; projection -> its dgrad
                 if ds_join is not None:
                     ds_join[0].wait_event(ds_join[1])
-                    addend = ds_join[2]
-                elif ds_cfg is not None:
-                    addend = shortcut_backward(g_short)
+                elif shortcut is not None:
+                    addend = bw.shortcut(shortcut, g_short, x, sums_ds)
                 else:
                     addend = g_short
-                if not ctx.needs_input_grad[0]:
-                    dz = None
-                else:
-                    hi = ctx.handoff_in
-                    sg = _grad_sink(hi.gamma) if hi is not None else None
-                    sb = _grad_sink(hi.beta) if hi is not None else None
-                    if sg is not None and sb is not None and _BN_HANDOFF and _FUSE_DGRAD_BN:
-                        # previous block's last unit: relu mask from its output z = x
-                        zsrc, zmode = (hi.zmask, 3) if hi.zmask is not None else (x, 1)
-                        if _BN_ACC and not det:
-                            acc = _bacc(hi.gamma, hi.stats.shape[1])
-                            # the previous block's projection-shortcut BN reduced in the same epilogue
-                            ds2 = hi.ds if (hi.ds is not None and zmode == 3 and addend is not None
-                                            and (d8 is None or not _fp8_dgrad_ok(d8[0].shape[3], st))
-                                            and _grad_sink(hi.ds[2]) is not None) else None
-                            acc2 = _bacc(hi.ds[2], hi.stats.shape[1]) if ds2 is not None else None
-                            dz, sums_in = dgrad_bn_any(dy, d8, w, list(x.shape), st, pd, addend, hi.y, zsrc,
-                                                       hi.stats, zmode, acc=acc,
-                                                       bn2=(ds2[0], ds2[1], acc2) if ds2 is not None else None)
-                            hi.deposit = (dz, sums_in, acc, acc2)
-                        else:
-                            dz, sums_in = dgrad_bn_any(dy, d8, w, list(x.shape), st, pd, addend, hi.y, zsrc,
-                                                       hi.stats, zmode, sg, sb)
-                            hi.deposit = (dz, sums_in, None, None)
-                    else:
-                        dz = dgrad(dy, d8, w, list(x.shape), st, pd, addend)
+                dz = bw.dgrad_handoff(u, dy, d8, x, addend, ctx.handoff_in) if bw.needs_dx else None
         ctx.handoff_in = None
-        for acc_, _, _ in deferred.values():  # (every unit's weight gradient re-zeroes its own)
-            acc_.zero_()
+        for acc, _, _ in bw.deferred.values():  # (every unit's weight gradient re-zeroes its own)
+            acc.zero_()
         if ctx.colsum is not None:  # summed in forward but not folded (no hand-off into this block)
             if ctx.colsum.dim() == 2:  # the atomic slots must be left zeroed
                 ctx.colsum.zero_()
             ctx.colsum = None
-        if sunk:
-            sunk[0]._pdt_flat.mark_ready(sunk)
-        return (dz, None, None, None, *grads)
+        if bw.sunk:
+            bw.sunk[0]._pdt_flat.mark_ready(bw.sunk)
+        return (dz, None, None, None, *bw.grads)
 
 
-# Fold the last unit's BN backward into its 1x1 input gradient (DgradFold) -- ResNet-50 b256 in the
-# same calls: 18.15 vs 18.29 and 18.27 vs 18.54 ms/step (r6r / r6s); removing that apply altogether
-# bounds the gain at 1.47 ms (r6f), the rest is spent in the fold-weight kernels on the critical
-# stream (~20 us per block in-step) and the larger dgrad K.
-_FOLD_BN = True
-FOLD_CALLS = 0  # folded units so far (tests check that the path engaged)
+def _fold_shape_ok(u) -> bool:
+    """Is unit u's conv one the DgradFold kernels take: training, 1x1 / stride 1, K a multiple of 256
+    up to 2048, C a multiple of 64?"""
+    k, c, r, s = u.w.shape
+    return (u.training and r == 1 and s == 1 and u.stride == 1 and u.pad == 0 and k % 256 == 0 and k <= 2048
+            and c % 64 == 0)
 
 
-def _fold_ok(i, last, w, xin, st, pd, tr, det, side, fp8b, params) -> bool:
-    """May the last unit of a bottleneck fold its BN backward into its 1x1 input gradient
+def _fold_ok(u, prev, xin, bw) -> bool:
+    """May the last unit u of a bottleneck fold its BN backward into its 1x1 input gradient
     (kernels.h DgradFold)?  bf16, training, a weight-gradient side stream, a 1x1 / stride-1 conv over
     a materialised input, and gradient sinks for the BN of the unit before (its sums go to an atomic
     accumulator, or in deterministic runs to fixed-order partials with dgamma / dbeta written by the
     reduce; the fold's weight-gradient GEMMs then take the slab split-K)."""
-    if not (_FOLD_BN and last and i > 0 and tr and side is not None and not fp8b and _BN_ACC
-            and _FUSE_DGRAD_BN and xin is not None):
+    if not (_FOLD_BN and _BN_ACC and bw.side is not None and not bw.fp8b and xin is not None
+            and _fold_shape_ok(u) and xin.shape[3] == u.w.shape[1]):
         return False
-    k, c, r, s_ = w.shape
-    if r != 1 or s_ != 1 or st != 1 or pd != 0 or k % 256 or k > 2048 or c % 64 or xin.shape[3] != c:
-        return False
-    j = 5 * (i - 1)
-    return (_grad_sink(params[j + 1]) is not None and _grad_sink(params[j + 2]) is not None
-            and _grad_sink(params[5 * i]) is not None)
+    return (_grad_sink(prev.p_gamma) is not None and _grad_sink(prev.p_beta) is not None
+            and _grad_sink(u.p_w) is not None)
 
 
-def _fold_colsum_ok(chain, tensors, x) -> bool:
+def _fold_colsum_ok(units, x) -> bool:
     """Will the last unit's folded weight gradient (DgradFold) want sum_m of its conv input?  The
     static half of _fold_ok: a training bottleneck whose last conv is a foldable 1x1, bf16, with a
     weight-gradient side stream and a flat-space gradient sink."""
-    nch = len(chain)
-    if nch < 2 or not x.is_cuda or _FP8 or not (_FOLD_BN and _BN_ACC and _FUSE_DGRAD_BN):
+    if len(units) < 2 or not x.is_cuda or _FP8 or not (_FOLD_BN and _BN_ACC):
         return False
-    st, pd, tr, _, _ = chain[-1]
-    w = tensors[5 * (nch - 1)]
-    k, c, r, s_ = w.shape
-    if not tr or r != 1 or s_ != 1 or st != 1 or pd != 0 or k % 256 or k > 2048 or c % 64 or 256 % (c // 8):
+    u = units[-1]
+    if not _fold_shape_ok(u) or 256 % (u.w.shape[1] // 8):
         return False
-    return streams.wgrad_stream(x.device) is not None and _grad_sink(w) is not None
+    return streams.wgrad_stream(x.device) is not None and _grad_sink(u.w) is not None
 
 
 def _csum_slots(w, dev):
@@ -1387,14 +1391,6 @@ def _zero_stats(c, dev):
     if z is None:
         z = _ZSTATS[(c, dev)] = torch.zeros(4, c, device=dev)
     return z
-
-
-def _grad_sink(p):
-    """Flat-buffer gradient view to accumulate into, if the parameter lives in a FlatParamSpace."""
-    sp = getattr(p, "_pdt_flat", None)
-    if sp is None or not p.requires_grad or not p.is_cuda:
-        return None
-    return sp.grad_sink(p)
 
 
 def _unit_tensors(conv: nn.Conv2d, bn: nn.BatchNorm2d) -> list:

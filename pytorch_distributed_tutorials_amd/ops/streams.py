@@ -9,7 +9,7 @@ stays on the caller's stream (it is the critical path of backward).
 Ordering: the side stream waits for the caller's stream before each wgrad (its
 inputs are ready); the inputs are ``record_stream``-ed so the caching allocator
 does not hand their memory out while the side stream still reads them -- all three
-in one native call, ``C.conv_wgrad_side`` (csrc/bindings.cpp); gradient
+in one native call, ``C.conv_wgrad_side`` (csrc/bind_conv.cpp); gradient
 all-reduces wait for the side stream (``Reducer.set_aux_stream``); and a callback
 at the end of backward joins it into the caller's stream, so the optimizer step
 sees every gradient.
