@@ -8,7 +8,11 @@
 * ``csrc/*.cpp`` (the module and one binding source per op family), ``csrc/comm/*.cpp``
   and ``csrc/ddp/*.cpp`` are host C++ compiled by hipcc against the installed PyTorch headers;
 * everything is linked into ``pytorch_distributed_tutorials_amd/_C<EXT_SUFFIX>``
-  against libtorch and the RCCL shipped inside the torch wheel, rpath'd to it.
+  against libtorch and the RCCL shipped inside the torch wheel, rpath'd to it;
+* ``csrc/mix/*`` (the MixUp / CutMix ops) is built the same way, with the same flags, into a second
+  module ``pytorch_distributed_tutorials_amd/_C_mix<EXT_SUFFIX>`` whose objects live in
+  ``build/native_mix`` (the public surface of ``_C`` is pinned, and other tools link every object of
+  ``build/native`` into ``_C``).
 
 Incremental: an object is rebuilt when its source or any header under csrc/ is
 newer, and an object whose source is gone is deleted (other tools link every object of the build
@@ -35,6 +39,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(ROOT, "csrc")
 PKG = os.path.join(ROOT, "pytorch_distributed_tutorials_amd")
 BUILD = os.path.join(ROOT, "build", "native")
+BUILD_MIX = os.path.join(ROOT, "build", "native_mix")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -70,19 +75,20 @@ def asan_out_path() -> str:
     return os.path.join(ROOT, "build", "asan", "_C" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 
-def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool = True,
-          sanitize: bool = False) -> str:
-    tdir, tinc, abi = _torch_paths()
-    bdir = os.path.join(ROOT, "build", "native_asan") if sanitize else BUILD
+def mix_out_path() -> str:
+    return os.path.join(PKG, "_C_mix" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
+def asan_mix_out_path() -> str:
+    return os.path.join(ROOT, "build", "asan", "_C_mix" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
+def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc, tdir, force, jobs, verbose,
+                  sanitize):
+    """Compile the stale objects of one extension module into ``bdir`` and link them into ``so``."""
     os.makedirs(bdir, exist_ok=True)
-    opt = ["-O0", "-g"] if debug else (["-O1", "-g"] + SAN_FLAGS if sanitize else ["-O3"])
-    common = ["-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1",
-              "-Wno-unused-result", "-Wno-unused-value"] + opt
-    kern_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
-    host_srcs = sorted(glob.glob(os.path.join(CSRC, "*.cpp"))) + sorted(
-        glob.glob(os.path.join(CSRC, "comm", "*.cpp")) + glob.glob(os.path.join(CSRC, "ddp", "*.cpp")))
     py_inc = sysconfig.get_paths()["include"]
-    host_flags = common + [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C",
+    host_flags = common + [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DUSE_ROCM=1", f"-DTORCH_EXTENSION_NAME={name}",
                            "-DTORCH_API_INCLUDE_EXTENSION_H", "-I", py_inc, "-I", CSRC,
                            "-I", "/opt/rocm/include"] + sum((["-I", i] for i in tinc), [])
     hdr_t = _newest_header()
@@ -112,18 +118,39 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                     print(f"[build_native]   ok {os.path.relpath(futs[f], ROOT)}", flush=True)
     for old in set(glob.glob(os.path.join(bdir, "*.o"))) - set(objs):
         os.remove(old)  # its source was removed or renamed
-    so = asan_out_path() if sanitize else out_path()
     os.makedirs(os.path.dirname(so), exist_ok=True)
     if force or jobs_list or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(o) for o in objs):
         tlib = os.path.join(tdir, "lib")
         link = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", so] + objs + [
-            "-L", tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python",
-            os.path.join(tlib, "librccl.so"), f"-Wl,-rpath,{tlib}", "-Wl,-rpath,/opt/rocm/lib"]
+            "-L", tlib, "-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-ltorch_python"] + \
+            [os.path.join(tlib, lib) for lib in libs] + [f"-Wl,-rpath,{tlib}", "-Wl,-rpath,/opt/rocm/lib"]
         if sanitize:
             link += ["-fsanitize=address,undefined", "-shared-libsan"]
         _run(link)
         if verbose:
             print(f"[build_native] linked {os.path.relpath(so, ROOT)}", flush=True)
+    return so
+
+
+def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool = True,
+          sanitize: bool = False) -> str:
+    """Build both extension modules, ``_C`` and ``_C_mix``; returns the path of ``_C``."""
+    tdir, tinc, abi = _torch_paths()
+    opt = ["-O0", "-g"] if debug else (["-O1", "-g"] + SAN_FLAGS if sanitize else ["-O3"])
+    common = ["-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1",
+              "-Wno-unused-result", "-Wno-unused-value"] + opt
+    kern_srcs = sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
+    host_srcs = sorted(glob.glob(os.path.join(CSRC, "*.cpp"))) + sorted(
+        glob.glob(os.path.join(CSRC, "comm", "*.cpp")) + glob.glob(os.path.join(CSRC, "ddp", "*.cpp")))
+    rest = (common, abi, tinc, tdir, force, jobs, verbose, sanitize)
+    so = _build_module("_C", kern_srcs, host_srcs, os.path.join(ROOT, "build", "native_asan") if sanitize else BUILD,
+                       asan_out_path() if sanitize else out_path(), ["librccl.so"], *rest)
+    # the batch-mixing ops: a module and an object directory of their own (other tools link every
+    # object they find in build/native into _C)
+    _build_module("_C_mix", sorted(glob.glob(os.path.join(CSRC, "mix", "*.hip"))),
+                  sorted(glob.glob(os.path.join(CSRC, "mix", "*.cpp"))),
+                  os.path.join(ROOT, "build", "native_mix_asan") if sanitize else BUILD_MIX,
+                  asan_mix_out_path() if sanitize else mix_out_path(), [], *rest)
     return so
 
 

@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from .datasets import TensorImageDataset
+from .mix import MixConfig, MixDraw, MixedTarget, draw_mix, mix_batch
 
 
 def _normalize(x: torch.Tensor, mean, std) -> torch.Tensor:
@@ -52,12 +53,20 @@ def random_crop_flip(x: torch.Tensor, pad: int, gen: Optional[torch.Generator]) 
 
 
 class DeviceLoader:
-    """Iterates ``(images[B,3,H,W] float32, labels[B] int64)`` batches on ``device``."""
+    """Iterates ``(images[B,3,H,W] float32, labels[B] int64)`` batches on ``device``.
+
+    With ``mix=MixConfig(...)`` the batch is mixed per sample (MixUp / CutMix, ``data/mix.py``) and
+    comes as ``(images, MixedTarget)``: one ``augment_mix`` kernel on the fused path, the chain
+    below followed by ``mix_batch`` on the torch path, both fed by the same ``draw_mix`` draws made
+    after the batch's crop/flip draws.  Evaluation loaders pass no ``mix``."""
 
     def __init__(self, dataset: TensorImageDataset, batch_size: int, sampler=None,
                  shuffle: bool = False, augment: bool = False, device="cpu",
-                 drop_last: bool = False, seed: int = 0, fused: Optional[bool] = None):
+                 drop_last: bool = False, seed: int = 0, fused: Optional[bool] = None,
+                 mix: Optional[MixConfig] = None):
         self.ds = dataset.to(device)
+        # MixUp / CutMix (data/mix.py): batches come as (images, MixedTarget); None = hard labels
+        self.mix = MixConfig(*mix).validate() if mix is not None else None
         self.batch_size = batch_size
         self.sampler = sampler
         self.shuffle = shuffle
@@ -96,6 +105,13 @@ class DeviceLoader:
         if self.augment:
             gen = torch.Generator(device=self.device)
             gen.manual_seed(self.seed * 1000003 + self.epoch)
+        mgen = None
+        if self.mix is not None:
+            # the loader's second random stream: the mix draws of a batch come after its crop/flip
+            # draws and never advance their stream, so every batch of a mixing run sees the crops
+            # and flips the same run without mixing sees
+            mgen = torch.Generator(device=self.device)
+            mgen.manual_seed((self.seed * 1000003 + self.epoch) ^ 0x4D6978)
         idx = idx.to(self.device)
         n = idx.numel()
         stop = (n // self.batch_size) * self.batch_size if self.drop_last else n
@@ -103,7 +119,8 @@ class DeviceLoader:
             bi = idx[s:s + self.batch_size]
             y = self.ds.labels.index_select(0, bi)
             if self.fused:
-                yield self._fused_batch(bi, gen), y
+                x, draw = self._fused_batch(bi, gen, mgen)
+                yield x, self._target(y, draw)
                 continue
             x = self.ds.images.index_select(0, bi)
             if not self.ds.normalized:
@@ -113,10 +130,26 @@ class DeviceLoader:
                 x = _normalize(x, self.ds.mean, self.ds.std)
             elif self.augment:
                 x = random_crop_flip(x, 4, gen)
-            yield x.float().contiguous(), y
+            x = x.float().contiguous()
+            draw = self._draw_mix(bi.numel(), mgen)
+            if draw is not None:
+                x = mix_batch(x, draw.partner, draw.w, draw.box)
+            yield x, self._target(y, draw)
 
-    def _fused_batch(self, bi: torch.Tensor, gen) -> torch.Tensor:
-        from ..ops._ext import native
+    def _draw_mix(self, b: int, gen) -> Optional[MixDraw]:
+        if self.mix is None:
+            return None
+        h, w = self.ds.images.shape[2], self.ds.images.shape[3]
+        return draw_mix(b, h, w, *self.mix, device=self.device, gen=gen)
+
+    @staticmethod
+    def _target(y: torch.Tensor, draw: Optional[MixDraw]):
+        if draw is None:
+            return y
+        return MixedTarget(y, y.index_select(0, draw.partner), draw.lam)
+
+    def _fused_batch(self, bi: torch.Tensor, gen, mgen=None) -> Tuple[torch.Tensor, Optional[MixDraw]]:
+        from ..ops._ext import native, native_mix
         b = bi.numel()
         if self.augment:
             oy, ox, flip = draw_crop_flip(b, 4, self.device, gen)
@@ -127,5 +160,11 @@ class DeviceLoader:
         imgs = self.ds.images
         if imgs.dtype not in (torch.uint8, torch.float32):
             imgs = imgs.float()
-        return native().augment(imgs.contiguous(), bi.contiguous(), oy, ox, flip, pad,
-                                not self.ds.normalized, list(self.ds.mean), list(self.ds.std))
+        draw = self._draw_mix(b, mgen)
+        if draw is None:
+            return native().augment(imgs.contiguous(), bi.contiguous(), oy, ox, flip, pad,
+                                    not self.ds.normalized, list(self.ds.mean), list(self.ds.std)), None
+        x = native_mix().augment_mix(imgs.contiguous(), bi.contiguous(), oy, ox, flip, pad,
+                                     not self.ds.normalized, list(self.ds.mean), list(self.ds.std),
+                                     draw.partner, draw.w, draw.box)
+        return x, draw

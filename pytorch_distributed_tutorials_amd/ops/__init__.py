@@ -4,9 +4,10 @@ See ``fused.py`` for the autograd units and ``reference.py`` for the PyTorch
 semantics they implement.  ``native_available()`` reports whether the gfx950
 extension loaded.
 """
-from ._ext import native, native_available  # noqa: F401
+from ._ext import native, native_available, native_mix, native_mix_available  # noqa: F401
 from .fused import (  # noqa: F401
     CrossEntropyLoss,
+    mix_cross_entropy,
     act_dtype,
     avgpool_linear,
     buffers_ready,

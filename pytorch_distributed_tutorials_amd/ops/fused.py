@@ -24,8 +24,9 @@ import torch.nn as nn
 
 from . import reference as ref
 from . import streams
+from ..data.mix import MixedTarget
 from ..utils.seed import deterministic
-from ._ext import native
+from ._ext import native, native_mix
 
 _CPU_DTYPE = torch.float32  # activation dtype of the CPU reference path
 # Module switches: the ones tests, scripts or the README's knob table set.
@@ -629,14 +630,48 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: f
     return _SoftmaxXent.apply(logits, labels, label_smoothing)
 
 
+class _SoftmaxXentMix(torch.autograd.Function):
+    """``_SoftmaxXent`` against the two-label target of a mixed batch (``data/mix.py``)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_a, labels_b, lam, label_smoothing=0.0):
+        if logits.is_cuda:
+            loss, dlogits = native_mix().softmax_xent_mix(logits.contiguous(), labels_a.contiguous(),
+                                                          labels_b.contiguous(), lam.float().contiguous(),
+                                                          float(label_smoothing))
+        else:
+            loss, dlogits = ref.softmax_xent_mix(logits, labels_a, labels_b, lam, label_smoothing)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dlogits,) = ctx.saved_tensors
+        if dlogits.is_cuda:  # scaled on the device by the (device) loss gradient: no host sync
+            return native().scale_by(dlogits, dloss.float().reshape(1)), None, None, None, None
+        return dlogits * dloss, None, None, None, None
+
+
+def mix_cross_entropy(logits: torch.Tensor, labels_a: torch.Tensor, labels_b: torch.Tensor, lam: torch.Tensor,
+                      label_smoothing: float = 0.0) -> torch.Tensor:
+    """Mean cross entropy against lam onehot(labels_a) + (1 - lam) onehot(labels_b), ``lam`` per
+    row: ``F.cross_entropy`` with that soft target and ``label_smoothing``."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    return _SoftmaxXentMix.apply(logits, labels_a, labels_b, lam, label_smoothing)
+
+
 class CrossEntropyLoss(nn.Module):
-    """Drop-in for ``nn.CrossEntropyLoss()`` (mean reduction, ``resnet/main.py:102``)."""
+    """Drop-in for ``nn.CrossEntropyLoss()`` (mean reduction, ``resnet/main.py:102``); the target
+    is a label tensor or the ``MixedTarget`` of a mixed batch."""
 
     def __init__(self, label_smoothing: float = 0.0):
         super().__init__()
         self.label_smoothing = float(label_smoothing)
 
-    def forward(self, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def forward(self, logits: torch.Tensor, labels) -> torch.Tensor:
+        if isinstance(labels, MixedTarget):
+            return mix_cross_entropy(logits, labels.labels_a, labels.labels_b, labels.lam, self.label_smoothing)
         return cross_entropy(logits, labels, self.label_smoothing)
 
 

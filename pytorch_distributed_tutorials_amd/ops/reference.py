@@ -128,6 +128,33 @@ def softmax_xent(logits: torch.Tensor, labels: torch.Tensor,
     return loss, p / lf.shape[0]
 
 
+def softmax_xent_mix(logits: torch.Tensor, labels_a: torch.Tensor, labels_b: torch.Tensor, lam: torch.Tensor,
+                     label_smoothing: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``softmax_xent`` against the two-label target lam onehot(a) + (1-lam) onehot(b) (MixUp /
+    CutMix, ``data/mix.py``), smoothed as there.  Row loss
+    hit (lam (lse - x[a]) + (1-lam) (lse - x[b])) + eps (lse - mean x) with hit = 1 - eps, written
+    as the loss on ``labels_a`` plus hit (1-lam) (x[a] - x[b]); gradient
+    (softmax - hit lam 1[a] - hit (1-lam) 1[b] - eps/V) / N, the two terms adding where a == b.
+    With lam == 1 on every row both are ``softmax_xent(logits, labels_a)`` bit for bit."""
+    lf = logits.float()
+    n, v = lf.shape
+    rows = torch.arange(n, device=lf.device)
+    lam = lam.float()
+    hit = 1.0 - label_smoothing
+    xa, xb = lf[rows, labels_a], lf[rows, labels_b]
+    if label_smoothing == 0.0:
+        loss = F.cross_entropy(lf, labels_a) + ((1.0 - lam) * (xa - xb)).mean()
+        p = torch.softmax(lf, dim=1)
+        p[rows, labels_a] -= lam
+        p[rows, labels_b] -= 1.0 - lam
+        return loss, p / n
+    loss = F.cross_entropy(lf, labels_a, label_smoothing=label_smoothing) + hit * ((1.0 - lam) * (xa - xb)).mean()
+    p = torch.softmax(lf, dim=1) - label_smoothing / v
+    p[rows, labels_a] -= hit * lam
+    p[rows, labels_b] -= hit * (1.0 - lam)
+    return loss, p / n
+
+
 def top1_correct(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return (logits.argmax(1) == labels).sum()
 

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .data import DeviceLoader, DistributedSampler, build_dataset
+from .data import DeviceLoader, DistributedSampler, MixConfig, build_dataset
 from .models import build_model
 from .optim import LARS, SGD, WarmupPolyLR
 from .parallel import DistributedDataParallel, destroy, init_distributed
@@ -113,6 +113,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "polynomial (power 2) decay to --lr-end at the end of --num_epochs")
     p.add_argument("--warmup-epochs", type=float, default=5.0)
     p.add_argument("--lr-end", type=float, default=0.0)
+    # ---- input-side regularisers (off by default): per-sample MixUp / CutMix on the training batch
+    p.add_argument("--mixup-alpha", type=float, default=0.0,
+                   help="MixUp: blend each sample with its batch neighbour, weight ~ Beta(alpha, alpha); 0 = off")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0,
+                   help="CutMix: paste a box of the batch neighbour, area from Beta(alpha, alpha); 0 = off")
+    p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a sample is mixed at all")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5,
+                   help="with both alphas set: probability that a mixed sample takes CutMix rather than MixUp")
     return p
 
 
@@ -205,6 +213,15 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(f"--graph cannot follow --lr-schedule {args.lr_schedule}: the captured step bakes "
                          "the learning rate in, so a schedule would re-capture it every step; use "
                          "--lr-schedule constant with --graph")
+    try:
+        mix = MixConfig(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.mix_switch_prob).validate()
+    except ValueError as e:
+        raise SystemExit(f"--mixup-alpha / --cutmix-alpha / --mix-prob / --mix-switch-prob: {e}")
+    mix = mix if mix.enabled else None
+    if args.graph and mix is not None:
+        # _GraphStep keeps one static label tensor; a mixed batch carries two labels and a weight per row
+        raise SystemExit("--graph cannot be combined with --mixup-alpha / --cutmix-alpha: the captured step "
+                         "holds one static label tensor, not a mixed target; run mixing without --graph")
     set_random_seeds(args.seed, deterministic=args.deterministic)
     env = init_distributed(args.backend, args.local_rank, args.timeout)
     local_rank = env.local_rank
@@ -253,7 +270,9 @@ def main(argv: Optional[list] = None) -> int:
                                         bucket_cap_mb=args.bucket_mb, wire_dtype=args.wire_dtype,
                                         comm_options=CommOptions.from_env(timeout=args.timeout))
     holder["ddp"] = ddp_model
-    if args.label_smoothing != 0.0:
+    if mix is not None:  # the two-label target: ops.CrossEntropyLoss for both impls (CPU = reference)
+        criterion = ops.CrossEntropyLoss(label_smoothing=args.label_smoothing)
+    elif args.label_smoothing != 0.0:
         criterion = ops.CrossEntropyLoss(label_smoothing=args.label_smoothing) if impl == "native" \
             else nn.CrossEntropyLoss(label_smoothing=args.label_smoothing)
     else:
@@ -290,7 +309,7 @@ def main(argv: Optional[list] = None) -> int:
                              seed=args.seed)
     train_sampler = DistributedSampler(len(train_set), num_replicas=env.world_size, rank=env.rank)
     train_loader = DeviceLoader(train_set, args.batch_size, sampler=train_sampler, augment=True,
-                                device=device, seed=args.seed + env.rank)
+                                device=device, seed=args.seed + env.rank, mix=mix)
     test_loader = DeviceLoader(test_set, 128, shuffle=False, augment=False, device=device)
 
     graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1) \
