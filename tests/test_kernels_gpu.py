@@ -3,6 +3,10 @@
 Inputs are rounded to bf16 first so the reference sees exactly the kernel's
 operands; tolerances cover the fp32-accumulate vs fp32-reference ordering and the
 final bf16 rounding of outputs.
+
+The conv tests' whole-tensor norm ratio cannot see a localized error (a zeroed GEMM row measures
+0.008 at two of CONV_SHAPES and passes): tests/test_conv_exact_gpu.py pins the same kernels bit for
+bit on integer operands, tile by tile and loader by loader.
 """
 import pytest
 import torch

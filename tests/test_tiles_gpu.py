@@ -64,8 +64,8 @@ def test_fwd_stats_per_tile(gpu, native_ext, shape, tile):
     C = native_ext
     n, h, w, c, k, r, s, st, pd = shape
     x, wt, _ = _operands(shape, gpu, 1)
-    ho = (h + 2 * pd - r) // st + 1
-    M = n * ho * ho
+    ho, wo = (h + 2 * pd - r) // st + 1, (w + 2 * pd - s) // st + 1
+    M = n * ho * wo
     assert tuple(C.conv_nt_tile(M, k, r * s * c * 2)) == tile
     y, part = C.conv_fwd(x, C.pack_weight(wt, c), st, pd, True)
     yr = ref.conv2d_nhwc(x, wt, st, pd)
