@@ -1,4 +1,4 @@
-"""Datasets: synthetic (ImageNet / CIFAR shaped) and CIFAR-10 from disk.
+"""Datasets: synthetic (ImageNet / CIFAR shaped), CIFAR-10 from disk and prepared uint8 arrays.
 
 The reference reads CIFAR-10 through torchvision with ``download=False``
 (``resnet/main.py:94-95``) and augments on 8 CPU worker processes with PIL
@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import os
 import pickle
+import warnings
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -114,13 +115,46 @@ def cifar10(root: str = "data", train: bool = True) -> TensorImageDataset:
     return TensorImageDataset(torch.from_numpy(data), torch.from_numpy(labels))
 
 
+def array_dataset(root: str = "data", train: bool = True) -> TensorImageDataset:
+    """A prepared image set from ``root``: ``{train,val}_images.npy``, uint8 ``[N, 3, H, W]`` (decoded
+    and down-sized ahead of time, e.g. ImageNet at 128 or 256 pixels: there is no JPEG decoding
+    here), and ``{train,val}_labels.npy``, integer ``[N]``.  The images are memory-mapped, so the one
+    copy that is made is the one onto the device; normalization uses the ImageNet statistics."""
+    split = "train" if train else "val"
+    paths = [os.path.join(root, f"{split}_{what}.npy") for what in ("images", "labels")]
+    for p in paths:
+        if not os.path.isfile(p):
+            raise FileNotFoundError(
+                f"array dataset: {p!r} not found (expected {split}_images.npy, uint8 [N, 3, H, W], and "
+                f"{split}_labels.npy, integer [N], under {root!r})")
+    images = np.load(paths[0], mmap_mode="r", allow_pickle=False)
+    labels = np.load(paths[1], mmap_mode="r", allow_pickle=False)
+    if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1] != 3 or 0 in images.shape:
+        raise ValueError(f"array dataset: {paths[0]!r} must hold uint8 [N, 3, H, W] images, "
+                         f"got {images.dtype} {tuple(images.shape)}")
+    if not np.issubdtype(labels.dtype, np.integer) or labels.ndim != 1 or labels.shape[0] != images.shape[0]:
+        raise ValueError(f"array dataset: {paths[1]!r} must hold integer [N] labels for the {images.shape[0]} "
+                         f"images, got {labels.dtype} {tuple(labels.shape)}")
+    labels = np.asarray(labels).astype(np.int64)
+    if labels.min() < 0:
+        raise ValueError(f"array dataset: {paths[1]!r} holds negative labels")
+    with warnings.catch_warnings():
+        # the map is read-only and torch warns about writes through the tensor; nothing writes to it
+        warnings.filterwarnings("ignore", message="The given NumPy array is not writable")
+        imgs = torch.from_numpy(images)
+    return TensorImageDataset(imgs, torch.from_numpy(labels), IMAGENET_MEAN, IMAGENET_STD)
+
+
 def build_dataset(kind: str, train: bool, root: str = "data", num_samples: Optional[int] = None,
                   image_size: Optional[int] = None, num_classes: int = 10,
                   seed: int = 0) -> TensorImageDataset:
-    """kind: 'cifar10' (disk), 'synthetic-cifar' (32px), 'synthetic-imagenet' (224px), or
-    'learnable-cifar' (32px class templates + noise: a set the model can fit)."""
+    """kind: 'cifar10' (disk), 'array' (prepared uint8 arrays on disk), 'synthetic-cifar' (32px),
+    'synthetic-imagenet' (224px), or 'learnable-cifar' (32px class templates + noise: a set the
+    model can fit)."""
     if kind == "cifar10":
         return cifar10(root, train)
+    if kind == "array":
+        return array_dataset(root, train)
     if kind == "synthetic-cifar":
         n = num_samples or (50000 if train else 10000)
         return synthetic_dataset(n, image_size or 32, num_classes, seed=seed + (0 if train else 1))

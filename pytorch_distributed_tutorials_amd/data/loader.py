@@ -12,17 +12,24 @@ Evaluation uses no augmentation (reference defect D7 fixed).
 On the GPU the whole chain (gather by index, /255, pad+crop, flip, normalize) is ONE fused HIP
 kernel (``csrc/kernels/augment.hip``) fed with crop offsets and flips drawn exactly as the torch
 path draws them, so both paths produce identical batches (tests/test_kernels_gpu.py).
+
+With ``transform=`` the loader runs the ImageNet chain of ``data/resize.py`` instead: a box per
+sample (``RandomResizedCrop`` for training, ``CenterCropResize`` for evaluation) resized to a fixed
+output size, flipped and normalized -- one ``_C_img.resized_crop`` kernel on the GPU
+(``csrc/img/resample.hip``), ``resized_crop`` of ``data/resize.py`` otherwise, both fed by the same
+box and flip draws.
 """
 from __future__ import annotations
 
 import math
-from typing import Iterator, Optional, Sequence, Tuple
+from typing import Iterator, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn.functional as F
 
 from .datasets import TensorImageDataset
 from .mix import MixConfig, MixDraw, MixedTarget, draw_mix, mix_batch
+from .resize import CenterCropResize, RandomResizedCrop, center_box, draw_rrc, resized_crop
 
 
 def _normalize(x: torch.Tensor, mean, std) -> torch.Tensor:
@@ -58,12 +65,19 @@ class DeviceLoader:
     With ``mix=MixConfig(...)`` the batch is mixed per sample (MixUp / CutMix, ``data/mix.py``) and
     comes as ``(images, MixedTarget)``: one ``augment_mix`` kernel on the fused path, the chain
     below followed by ``mix_batch`` on the torch path, both fed by the same ``draw_mix`` draws made
-    after the batch's crop/flip draws.  Evaluation loaders pass no ``mix``."""
+    after the batch's crop/flip draws.  Evaluation loaders pass no ``mix``.
+
+    ``transform=RandomResizedCrop(...)`` replaces the pad-crop + flip chain of ``augment`` (which it
+    implies) by a random box resized to the transform's size and a flip;
+    ``transform=CenterCropResize(...)`` is the evaluation counterpart (no draws, ``augment`` must be
+    off).  Batches then have the transform's output size, and mix boxes are drawn for that size and
+    applied (``mix_batch``) to the transformed batch on both paths.  ``None`` changes nothing."""
 
     def __init__(self, dataset: TensorImageDataset, batch_size: int, sampler=None,
                  shuffle: bool = False, augment: bool = False, device="cpu",
                  drop_last: bool = False, seed: int = 0, fused: Optional[bool] = None,
-                 mix: Optional[MixConfig] = None):
+                 mix: Optional[MixConfig] = None,
+                 transform: Union[RandomResizedCrop, CenterCropResize, None] = None):
         self.ds = dataset.to(device)
         # MixUp / CutMix (data/mix.py): batches come as (images, MixedTarget); None = hard labels
         self.mix = MixConfig(*mix).validate() if mix is not None else None
@@ -79,7 +93,16 @@ class DeviceLoader:
         if fused is None:
             from ..ops._ext import native_available
             fused = self.device.type == "cuda" and native_available()
-        self.fused = bool(fused) and self.device.type == "cuda" and self.ds.images.shape[3] % 4 == 0
+        if transform is not None:
+            if not isinstance(transform, (RandomResizedCrop, CenterCropResize)):
+                raise ValueError(f"transform must be RandomResizedCrop, CenterCropResize or None, got {transform!r}")
+            if augment and isinstance(transform, CenterCropResize):
+                raise ValueError("CenterCropResize is an evaluation transform: it cannot follow augment=True")
+            transform.validate()
+        self.transform = transform
+        # size of the batches (the 16-byte stores of the fused kernels need a width that is a multiple of 4)
+        self.out_hw = tuple(self.ds.images.shape[2:]) if transform is None else transform.out_hw
+        self.fused = bool(fused) and self.device.type == "cuda" and self.out_hw[1] % 4 == 0
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -102,7 +125,7 @@ class DeviceLoader:
     def __iter__(self) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
         idx = torch.tensor(self._indices(), dtype=torch.long)
         gen = None
-        if self.augment:
+        if self.augment or isinstance(self.transform, RandomResizedCrop):
             gen = torch.Generator(device=self.device)
             gen.manual_seed(self.seed * 1000003 + self.epoch)
         mgen = None
@@ -123,7 +146,14 @@ class DeviceLoader:
                 yield x, self._target(y, draw)
                 continue
             x = self.ds.images.index_select(0, bi)
-            if not self.ds.normalized:
+            if self.transform is not None:
+                box, flip = self._draw_transform(bi.numel(), gen)
+                x = x.float()
+                if not self.ds.normalized:
+                    x = _normalize(resized_crop(x.div_(255.0), box, self.out_hw, flip), self.ds.mean, self.ds.std)
+                else:
+                    x = resized_crop(x, box, self.out_hw, flip)
+            elif not self.ds.normalized:
                 x = x.float().div_(255.0)
                 if self.augment:
                     x = random_crop_flip(x, 4, gen)
@@ -139,8 +169,16 @@ class DeviceLoader:
     def _draw_mix(self, b: int, gen) -> Optional[MixDraw]:
         if self.mix is None:
             return None
+        return draw_mix(b, *self.out_hw, *self.mix, device=self.device, gen=gen)
+
+    def _draw_transform(self, b: int, gen):
+        """The boxes and flips of one batch under ``transform``: RandomResizedCrop draws the boxes
+        (``draw_rrc``), then the flips, from the crop generator; CenterCropResize draws nothing."""
         h, w = self.ds.images.shape[2], self.ds.images.shape[3]
-        return draw_mix(b, h, w, *self.mix, device=self.device, gen=gen)
+        if isinstance(self.transform, CenterCropResize):
+            return center_box(b, h, w, self.transform.crop_pct, self.device), None
+        box = draw_rrc(b, h, w, self.transform.scale, self.transform.ratio, self.device, gen)
+        return box, torch.rand((b,), device=self.device, generator=gen) < 0.5
 
     @staticmethod
     def _target(y: torch.Tensor, draw: Optional[MixDraw]):
@@ -149,8 +187,19 @@ class DeviceLoader:
         return MixedTarget(y, y.index_select(0, draw.partner), draw.lam)
 
     def _fused_batch(self, bi: torch.Tensor, gen, mgen=None) -> Tuple[torch.Tensor, Optional[MixDraw]]:
-        from ..ops._ext import native, native_mix
+        from ..ops._ext import native, native_img, native_mix
         b = bi.numel()
+        if self.transform is not None:
+            box, flip = self._draw_transform(b, gen)
+            imgs = self.ds.images
+            if imgs.dtype not in (torch.uint8, torch.float32):
+                imgs = imgs.float()
+            x = native_img().resized_crop(imgs.contiguous(), bi.contiguous(), box, flip, *self.out_hw,
+                                          not self.ds.normalized, list(self.ds.mean), list(self.ds.std))
+            draw = self._draw_mix(b, mgen)
+            if draw is not None:
+                x = mix_batch(x, draw.partner, draw.w, draw.box)
+            return x, draw
         if self.augment:
             oy, ox, flip = draw_crop_flip(b, 4, self.device, gen)
             pad = 4

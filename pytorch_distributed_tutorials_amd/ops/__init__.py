@@ -4,7 +4,8 @@ See ``fused.py`` for the autograd units and ``reference.py`` for the PyTorch
 semantics they implement.  ``native_available()`` reports whether the gfx950
 extension loaded.
 """
-from ._ext import native, native_available, native_mix, native_mix_available  # noqa: F401
+from ._ext import (native, native_available, native_img, native_img_available, native_mix,  # noqa: F401
+                   native_mix_available)
 from .fused import (  # noqa: F401
     CrossEntropyLoss,
     mix_cross_entropy,

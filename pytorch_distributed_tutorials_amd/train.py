@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .data import DeviceLoader, DistributedSampler, MixConfig, build_dataset
+from .data import (CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
+                   build_dataset)
 from .models import build_model
 from .optim import LARS, SGD, WarmupPolyLR
 from .parallel import DistributedDataParallel, destroy, init_distributed
@@ -71,7 +72,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--impl", default="auto", choices=["auto", "native", "torch"],
                    help="native = MI355X HIP kernels (GPU); torch = stock ATen ops")
     p.add_argument("--data", default="cifar10",
-                   choices=["cifar10", "synthetic-cifar", "synthetic-imagenet", "learnable-cifar"])
+                   choices=["cifar10", "synthetic-cifar", "synthetic-imagenet", "learnable-cifar", "array"],
+                   help="array = --data-root/{train,val}_images.npy (uint8 [N,3,H,W]) + {train,val}_labels.npy")
     p.add_argument("--data-root", default="data")
     p.add_argument("--synthetic-samples", type=int, default=None)
     p.add_argument("--backend", default=None, choices=[None, "nccl", "gloo"])
@@ -121,7 +123,35 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mix-prob", type=float, default=1.0, help="probability that a sample is mixed at all")
     p.add_argument("--mix-switch-prob", type=float, default=0.5,
                    help="with both alphas set: probability that a mixed sample takes CutMix rather than MixUp")
+    # ---- input transforms (the defaults are the CIFAR recipe: pad-crop + flip, untransformed evaluation)
+    p.add_argument("--train-transform", default="pad-crop", choices=["pad-crop", "random-resized-crop"],
+                   help="random-resized-crop: a random box of --rrc-scale x the area and --rrc-ratio aspect, "
+                        "resized to --train-size, then a flip (the ImageNet recipe)")
+    p.add_argument("--train-size", type=int, default=None,
+                   help="output side of random-resized-crop and of the center-crop evaluation "
+                        "(default: the side of the stored images)")
+    p.add_argument("--rrc-scale", type=float, nargs=2, default=[0.08, 1.0], metavar=("LO", "HI"),
+                   help="random-resized-crop: range of the box area as a share of the image")
+    p.add_argument("--rrc-ratio", type=float, nargs=2, default=[3.0 / 4.0, 4.0 / 3.0], metavar=("LO", "HI"),
+                   help="random-resized-crop: range of the box aspect w / h (log-uniform)")
+    p.add_argument("--eval-transform", default="none", choices=["none", "center-crop"],
+                   help="center-crop: evaluate on the centred --eval-crop-pct box resized to --train-size")
+    p.add_argument("--eval-crop-pct", type=float, default=0.875)
     return p
+
+
+def input_transforms(args, image_hw):
+    """(train, eval) loader transforms of the parsed flags, None where the CIFAR chain stays; raises
+    ValueError on a bad size or range.  ``image_hw`` sizes the output when --train-size is not given."""
+    size = (args.train_size, args.train_size) if args.train_size is not None else tuple(image_hw)
+    train = evalt = None
+    if args.train_size is not None and args.train_size < 1:
+        raise ValueError(f"--train-size must be positive, got {args.train_size}")
+    if args.train_transform == "random-resized-crop":
+        train = RandomResizedCrop(size, tuple(args.rrc_scale), tuple(args.rrc_ratio)).validate()
+    if args.eval_transform == "center-crop":
+        evalt = CenterCropResize(size, args.eval_crop_pct).validate()
+    return train, evalt
 
 
 class _GraphStep:
@@ -222,6 +252,10 @@ def main(argv: Optional[list] = None) -> int:
         # _GraphStep keeps one static label tensor; a mixed batch carries two labels and a weight per row
         raise SystemExit("--graph cannot be combined with --mixup-alpha / --cutmix-alpha: the captured step "
                          "holds one static label tensor, not a mixed target; run mixing without --graph")
+    try:  # ranges now, before anything is set up; the sizes again once the dataset is known
+        input_transforms(args, (1, 1))
+    except ValueError as e:
+        raise SystemExit(f"--train-size / --rrc-scale / --rrc-ratio / --eval-crop-pct: {e}")
     set_random_seeds(args.seed, deterministic=args.deterministic)
     env = init_distributed(args.backend, args.local_rank, args.timeout)
     local_rank = env.local_rank
@@ -307,10 +341,15 @@ def main(argv: Optional[list] = None) -> int:
                              None if n_train is None else max(n_train // 5, 1),
                              num_classes=min(args.num_classes, 10 if "cifar" in args.data else 1000),
                              seed=args.seed)
+    if args.data == "array" and int(max(train_set.labels.max(), test_set.labels.max())) >= args.num_classes:
+        raise SystemExit(f"--data array: labels reach {int(max(train_set.labels.max(), test_set.labels.max()))} "
+                         f"but --num-classes is {args.num_classes}")
+    train_tf, _ = input_transforms(args, train_set.images.shape[2:])
+    _, eval_tf = input_transforms(args, test_set.images.shape[2:])
     train_sampler = DistributedSampler(len(train_set), num_replicas=env.world_size, rank=env.rank)
     train_loader = DeviceLoader(train_set, args.batch_size, sampler=train_sampler, augment=True,
-                                device=device, seed=args.seed + env.rank, mix=mix)
-    test_loader = DeviceLoader(test_set, 128, shuffle=False, augment=False, device=device)
+                                device=device, seed=args.seed + env.rank, mix=mix, transform=train_tf)
+    test_loader = DeviceLoader(test_set, 128, shuffle=False, augment=False, device=device, transform=eval_tf)
 
     graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1) \
         if args.graph else None
