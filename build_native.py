@@ -14,7 +14,9 @@
   ``build/native_mix`` (the public surface of ``_C`` is pinned, and other tools link every object of
   ``build/native`` into ``_C``);
 * ``csrc/img/*`` (the resampling input transform) likewise, into a third module ``_C_img<EXT_SUFFIX>``
-  with its objects in ``build/native_img``.
+  with its objects in ``build/native_img``;
+* ``csrc/ema/*`` (the weight-EMA update) likewise, into a fourth module ``_C_ema<EXT_SUFFIX>`` with
+  its objects in ``build/native_ema``.
 
 Incremental: an object is rebuilt when its source or any header under csrc/ is
 newer, and an object whose source is gone is deleted (other tools link every object of the build
@@ -43,6 +45,7 @@ PKG = os.path.join(ROOT, "pytorch_distributed_tutorials_amd")
 BUILD = os.path.join(ROOT, "build", "native")
 BUILD_MIX = os.path.join(ROOT, "build", "native_mix")
 BUILD_IMG = os.path.join(ROOT, "build", "native_img")
+BUILD_EMA = os.path.join(ROOT, "build", "native_ema")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -92,6 +95,14 @@ def img_out_path() -> str:
 
 def asan_img_out_path() -> str:
     return os.path.join(ROOT, "build", "asan", "_C_img" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
+def ema_out_path() -> str:
+    return os.path.join(PKG, "_C_ema" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
+def asan_ema_out_path() -> str:
+    return os.path.join(ROOT, "build", "asan", "_C_ema" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 
 def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc, tdir, force, jobs, verbose,
@@ -145,7 +156,7 @@ def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc,
 
 def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool = True,
           sanitize: bool = False) -> str:
-    """Build the extension modules ``_C``, ``_C_mix`` and ``_C_img``; returns the path of ``_C``."""
+    """Build the extension modules ``_C``, ``_C_mix``, ``_C_img`` and ``_C_ema``; returns the path of ``_C``."""
     tdir, tinc, abi = _torch_paths()
     opt = ["-O0", "-g"] if debug else (["-O1", "-g"] + SAN_FLAGS if sanitize else ["-O3"])
     common = ["-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1",
@@ -167,6 +178,11 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                   sorted(glob.glob(os.path.join(CSRC, "img", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_img_asan") if sanitize else BUILD_IMG,
                   asan_img_out_path() if sanitize else img_out_path(), [], *rest)
+    # the weight-EMA update: the same arrangement
+    _build_module("_C_ema", sorted(glob.glob(os.path.join(CSRC, "ema", "*.hip"))),
+                  sorted(glob.glob(os.path.join(CSRC, "ema", "*.cpp"))),
+                  os.path.join(ROOT, "build", "native_ema_asan") if sanitize else BUILD_EMA,
+                  asan_ema_out_path() if sanitize else ema_out_path(), [], *rest)
     return so
 
 

@@ -7,8 +7,9 @@ and FAILS LOUDLY when it is missing -- there is no silent eager fallback for
 device tensors.  CPU tensors use the PyTorch reference implementations (tests).
 
 The MixUp / CutMix ops live in a second module of the same build, ``_C_mix*.so``, and the
-resampling input transform in a third, ``_C_img*.so`` (the public surface of ``_C`` is pinned);
-``native_mix()`` and ``native_img()`` load them under the same rules.
+resampling input transform in a third, ``_C_img*.so``, and the weight-EMA update in a fourth,
+``_C_ema*.so`` (the public surface of ``_C`` is pinned); ``native_mix()``, ``native_img()`` and
+``native_ema()`` load them under the same rules.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ import importlib.util as importlib_util
 import os
 from typing import Any, Dict, Optional, Tuple
 
-# module name ("_C", "_C_mix", "_C_img") -> (module or None, the reason it failed to load or None)
+# module name ("_C", "_C_mix", "_C_img", "_C_ema") -> (module or None, the reason it failed to load or None)
 _MODULES: Dict[str, Tuple[Optional[Any], Optional[BaseException]]] = {}
 
 
@@ -69,6 +70,10 @@ def native_img_available() -> bool:
     return _load("_C_img")[0] is not None
 
 
+def native_ema_available() -> bool:
+    return _load("_C_ema")[0] is not None
+
+
 def native_mix() -> Any:
     """Return the batch-mixing extension module or raise with the reason it failed to load."""
     return _require("_C_mix")
@@ -77,6 +82,11 @@ def native_mix() -> Any:
 def native_img() -> Any:
     """Return the input-transform extension module or raise with the reason it failed to load."""
     return _require("_C_img")
+
+
+def native_ema() -> Any:
+    """Return the weight-EMA extension module or raise with the reason it failed to load."""
+    return _require("_C_ema")
 
 
 def native() -> Any:

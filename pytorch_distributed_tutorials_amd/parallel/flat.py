@@ -48,9 +48,12 @@ def forget_completed_side_packs() -> None:
 
 
 class FlatParamSpace:
-    def __init__(self, params: Sequence[torch.nn.Parameter], grad_flat: Optional[torch.Tensor] = None):
+    def __init__(self, params: Sequence[torch.nn.Parameter], grad_flat: Optional[torch.Tensor] = None,
+                 grads: bool = True):
         """``grad_flat``: caller-provided storage for the flat gradient buffer (e.g. the IPC-shared
-        buffer of the xGMI all-reduce backend); zeroed here."""
+        buffer of the xGMI all-reduce backend); zeroed here.  ``grads=False``: a space of weights
+        that are never trained (the averaged twin of ``optim.ModelEma``) -- no gradient buffer, no
+        gradient views, ``.grad`` left alone."""
         if not params:
             raise ValueError("FlatParamSpace needs at least one parameter")
         dev, dt = params[0].device, params[0].dtype
@@ -68,7 +71,11 @@ class FlatParamSpace:
         self.numel = off
         self.device, self.dtype = dev, dt
         self.param_flat = torch.empty(off, device=dev, dtype=dt)
-        if grad_flat is None:
+        if not grads:
+            if grad_flat is not None:
+                raise ValueError("a space without gradients takes no grad_flat")
+            self.grad_flat = None
+        elif grad_flat is None:
             self.grad_flat = torch.zeros(off, device=dev, dtype=dt)
         else:
             if grad_flat.numel() != off or grad_flat.dtype != dt or grad_flat.device != dev \
@@ -87,9 +94,11 @@ class FlatParamSpace:
                 view = torch.as_strided(self.param_flat, p.shape, p.stride(), o)
                 view.copy_(p.data)
                 p.data = view
-                self.grad_views.append(torch.as_strided(self.grad_flat, p.shape, p.stride(), o))
+                if grads:
+                    self.grad_views.append(torch.as_strided(self.grad_flat, p.shape, p.stride(), o))
                 p._pdt_flat = self  # noqa: SLF001  (marker read by optim.SGD)
-        self.attach_grads()
+        if grads:
+            self.attach_grads()
 
     def attach_grads(self) -> None:
         """(Re)point every ``p.grad`` at its view of the flat gradient buffer."""

@@ -30,7 +30,7 @@ from . import ops
 from .data import (CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
                    build_dataset)
 from .models import build_model
-from .optim import LARS, SGD, WarmupPolyLR
+from .optim import LARS, SGD, ModelEma, WarmupPolyLR
 from .parallel import DistributedDataParallel, destroy, init_distributed
 from .parallel.comm import CommOptions
 from .utils.checkpoint import load_checkpoint, save_checkpoint
@@ -137,6 +137,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-transform", default="none", choices=["none", "center-crop"],
                    help="center-crop: evaluate on the centred --eval-crop-pct box resized to --train-size")
     p.add_argument("--eval-crop-pct", type=float, default=0.875)
+    # ---- weight EMA (off by default): evaluated and checkpointed beside the raw weights
+    p.add_argument("--ema-decay", type=float, default=0.0,
+                   help="exponential moving average of the weights and BatchNorm statistics with this decay "
+                        "(optim.ModelEma), evaluated after the raw weights and saved as <name>.ema<ext>; 0 = off")
+    p.add_argument("--ema-every", type=int, default=1, help="update the EMA every N-th step")
+    p.add_argument("--ema-warmup", action="store_true",
+                   help="EMA decay min(--ema-decay, (1 + k) / (10 + k)) at update k")
     return p
 
 
@@ -256,6 +263,14 @@ def main(argv: Optional[list] = None) -> int:
         input_transforms(args, (1, 1))
     except ValueError as e:
         raise SystemExit(f"--train-size / --rrc-scale / --rrc-ratio / --eval-crop-pct: {e}")
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise SystemExit(f"--ema-decay must be in [0, 1) (0 = off), got {args.ema_decay}")
+    if args.ema_every < 1:
+        raise SystemExit(f"--ema-every must be at least 1, got {args.ema_every}")
+    if args.ema_decay > 0.0 and args.dtype == "fp8":
+        # the delayed-scaling slot rings are process-global: an evaluation of the twin would advance them
+        raise SystemExit("--ema-decay cannot be combined with --dtype fp8: the fp8 delayed-scaling state is "
+                         "process-global, so the EMA twin cannot be evaluated beside the model")
     set_random_seeds(args.seed, deterministic=args.deterministic)
     env = init_distributed(args.backend, args.local_rank, args.timeout)
     local_rank = env.local_rank
@@ -326,10 +341,14 @@ def main(argv: Optional[list] = None) -> int:
         optimizer = SGD(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
                         weight_decay=args.weight_decay, overlap=False if args.graph else None)
 
+    # every rank keeps its own, identical EMA (the parameters are the same everywhere): no collectives
+    ema = ModelEma(ddp_model, args.ema_decay, every=args.ema_every, warmup=args.ema_warmup) \
+        if args.ema_decay > 0.0 else None
+
     model_filepath = os.path.join(args.model_dir, args.model_filename)
     start_epoch = 0
     if args.resume:
-        ep = load_checkpoint(ddp_model, model_filepath, device, optimizer)
+        ep = load_checkpoint(ddp_model, model_filepath, device, optimizer, ema=ema)
         if ep is not None:
             start_epoch = int(ep)
 
@@ -381,10 +400,14 @@ def main(argv: Optional[list] = None) -> int:
             if device.type == "cuda":
                 torch.cuda.synchronize(device)
             ddp_model.check_comm()
-            save_checkpoint(ddp_model, model_filepath, optimizer, epoch)
+            save_checkpoint(ddp_model, model_filepath, optimizer, epoch, ema=ema)
             print("-" * 75)
             print("Epoch: {}, Accuracy: {}".format(epoch, accuracy))
             print("-" * 75, flush=True)
+            if ema is not None:
+                with trace.trace_range("eval_ema"):
+                    ema_accuracy = evaluate(model=ema.module, device=device, test_loader=test_loader)
+                print("Epoch: {}, EMA accuracy: {}".format(epoch, ema_accuracy), flush=True)
 
         ddp_model.train()
         train_loader.set_epoch(epoch)
@@ -417,6 +440,8 @@ def main(argv: Optional[list] = None) -> int:
                     loss.backward()
                 with trace.trace_range("optimizer"):
                     optimizer.step()
+            if ema is not None:  # eager also under --graph: warm-up and --ema-every stay host-side
+                ema.update()
             timer.tick()
             global_step += 1
             if args.log_every and (step + 1) % args.log_every == 0:
