@@ -34,15 +34,9 @@
 #include "kernels.h"
 
 #include <algorithm>
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
-#include <map>
-#include <mutex>
-#include <vector>
 
 namespace pdt {
 
@@ -1530,29 +1524,41 @@ __global__ void __launch_bounds__(256, 2) igemm_tn_f8_kernel(const TnF8Args P) {
 // ============================================================================
 //                                   host side
 // ============================================================================
-static void check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+// The NT workgroup tiles: the one place a (BM, BN) pair meets its template arguments.  WM x WN
+// waves of TM x TN MFMA tiles (plain and halo kernels), the depth of the tile's K32 ring, whether
+// its 2-stage K64 kernels (plain, fp8, halo) exist, and the wave grid of its quadrant-phased kernel
+// (0: none).  plan_nt() chooses among them; dispatch_nt() instantiates from the tag.
+template <int WM_, int WN_, int TM_, int TN_, int RING_, bool K64_ = true, int QWM_ = 0, int QWN_ = 0>
+struct NtTile {
+  static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, RING = RING_, QWM = QWM_, QWN = QWN_;
+  static constexpr bool K64 = K64_;
+  static constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
+  static constexpr int TMQ = QWM ? BM / (QWM * 32) : 0, TNQ = QWN ? BN / (QWN * 32) : 0;  // NtqCfg
+};
+constexpr int nt_tile_key(int bm, int bn) { return bm * 1024 + bn; }
+template <class F>
+static void with_nt_tile(int bm, int bn, F&& f) {
+  switch (nt_tile_key(bm, bn)) {
+    case nt_tile_key(256, 64): return f(NtTile<4, 1, 4, 4, 4>{});
+    case nt_tile_key(64, 128): return f(NtTile<2, 2, 2, 4, 4>{});
+    case nt_tile_key(128, 128): return f(NtTile<2, 2, 4, 4, 4, true, 2, 2>{});  // 64 KB, two blocks per CU
+    case nt_tile_key(128, 256): return f(NtTile<2, 2, 4, 8, 3, false>{});       // 72 KB, two blocks per CU
+    case nt_tile_key(256, 256): return f(NtTile<4, 2, 4, 8, 5, true, 2, 4>{});  // 8 waves, 160 KB ring
+  }
+  throw std::logic_error("no NT tile " + std::to_string(bm) + "x" + std::to_string(bn));
 }
 
-template <int WM, int WN, int TM, int TN, int STAGES, bool C64, int EPI, int OP = OP_BF16, bool K32 = false>
+template <class T, int STAGES, bool C64, int EPI, int OP = OP_BF16, bool K32 = false>
 static void run_nt(const NtArgs& a, hipStream_t st) {
-  using CFG = NtCfg<WM, WN, TM, TN, STAGES, K32>;
-  int ntm = (a.M + CFG::BM - 1) / CFG::BM;
-  int ntn = (a.Nout + CFG::BN - 1) / CFG::BN;
-  auto kfn = igemm_nt_kernel<WM, WN, TM, TN, STAGES, C64, EPI, OP, false, K32>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, CFG::SMEM);
-    attr_set = true;
-  }
+  using CFG = NtCfg<T::WM, T::WN, T::TM, T::TN, STAGES, K32>;
+  const int ntm = ceil_div(a.M, CFG::BM), ntn = ceil_div(a.Nout, CFG::BN);
   // a K loop shorter than the pipeline never touches the last buffers: request only the LDS it
   // uses so more blocks fit per CU (the short-K 1x1 convs are bound by their epilogue stores)
   constexpr int KE = OP == OP_BF16 ? (K32 ? 32 : 64) : 128;
   const int nk = C64 ? a.ntaps * (a.CA / KE) : (a.Kg + KE - 1) / KE;
   const int smem = std::max(std::max(1, std::min(nk, STAGES)) * CFG::STAGE_BYTES, CFG::EPI_BYTES);
-  hipLaunchKernelGGL(kfn, dim3(ntm * ntn), dim3(CFG::NT), smem, st, a);
-  check_launch("igemm_nt");
+  launch_lds<igemm_nt_kernel<T::WM, T::WN, T::TM, T::TN, STAGES, C64, EPI, OP, false, K32>>(
+      "igemm_nt", ntm * ntn, CFG::NT, CFG::SMEM, smem, st, a);
 }
 
 // The quadrant-phased kernel (igemm_ntq_kernel) runs the bf16 256x256 and 128x128 C64 tiles (r4ab,
@@ -1560,62 +1566,51 @@ static void run_nt(const NtArgs& a, hipStream_t st) {
 // removed in round 5 (git history: 242a23b): the ping-pong 256x256 kernel (won isolated GEMMs, lost
 // ~0.1 ms in the step), the read-ahead NTQ loop, stream-K for sub-wave grids (owners spun beside
 // the side-stream wgrads: 40 vs 19 ms/step) and the fp8 quadrant-phased tile.
-template <int WM, int WN, int TMQ, int TNQ, int EPI, int OP = OP_BF16>
+template <class T, int EPI>
 static void run_ntq(const NtArgs& a, hipStream_t st) {
-  using Q = NtqCfg<WM, WN, TMQ, TNQ>;
-  const int ntm = (a.M + Q::BM - 1) / Q::BM, ntn = (a.Nout + Q::BN - 1) / Q::BN;
-  auto kfn = igemm_ntq_kernel<WM, WN, TMQ, TNQ, EPI, OP>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, Q::SMEM);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3(ntm * ntn), dim3(Q::NT), Q::SMEM, st, a);
-  check_launch("igemm_ntq");
+  using Q = NtqCfg<T::QWM, T::QWN, T::TMQ, T::TNQ>;
+  static_assert(Q::BM == T::BM && Q::BN == T::BN, "quadrant-phased geometry of the tile");
+  const int ntm = ceil_div(a.M, Q::BM), ntn = ceil_div(a.Nout, Q::BN);
+  launch_lds<igemm_ntq_kernel<T::QWM, T::QWN, T::TMQ, T::TNQ, EPI, OP_BF16>>(
+      "igemm_ntq", ntm * ntn, Q::NT, Q::SMEM, Q::SMEM, st, a);
 }
 
-template <int WM, int WN, int TM, int TN, int EPI>
+template <class T, int EPI>
 static void run_nt_halo(const NtArgs& a, hipStream_t st) {
-  using CFG = NtCfg<WM, WN, TM, TN, 2>;
-  const int ntm = (a.M + CFG::BM - 1) / CFG::BM;
-  const int ntn = (a.Nout + CFG::BN - 1) / CFG::BN;
-  auto kfn = igemm_nt_kernel<WM, WN, TM, TN, 2, true, EPI, OP_BF16, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  using CFG = NtCfg<T::WM, T::WN, T::TM, T::TN, 2>;
+  const int ntm = ceil_div(a.M, CFG::BM), ntn = ceil_div(a.Nout, CFG::BN);
   const int smem = std::max((int)(a.halo_nbuf * a.halo_bytes) + 2 * CFG::BN * 128 + 128, CFG::EPI_BYTES);
-  hipLaunchKernelGGL(kfn, dim3(ntm * ntn), dim3(CFG::NT), smem, st, a);
-  check_launch("igemm_nt_halo");
+  launch_lds<igemm_nt_kernel<T::WM, T::WN, T::TM, T::TN, 2, true, EPI, OP_BF16, true>>(
+      "igemm_nt_halo", ntm * ntn, CFG::NT, 160 * 1024, smem, st, a);
 }
 
-// Halo staging for 3x3 / stride 1 / pad 1 convolutions (fwd and dgrad): fills the halo fields of
-// `a` for the tile the dispatcher will pick and returns false where it does not apply or does
-// not fit in LDS.
-static bool setup_halo(NtArgs& a, int R, int S, int tap_stride, int pad) {
-  // Measured on MI355X (r2p/r2q, bench_conv.py, batch 256): halo staging pays where one channel
-  // block covers the whole reduction (C = 64, ResNet layer1: fwd 114 -> 103 us, dgrad 111 -> 98,
-  // BN-fused dgrad 140 -> 130); with several channel blocks the halo reload per block stalls
-  // (128x28x28: 86 -> 93 us, 512x7x7: 75 -> 88), so those keep the per-tap A tiles.
-  if (R != 3 || S != 3 || tap_stride != 1 || pad != 1 || a.CA != 64 || !a.dense) return false;
-  int bm = 0, bn = 0;
-  conv_nt_tile(a.M, a.Nout, a.Kg * 2, &bm, &bn);
-  const int WP = a.WA + 2;
-  a.halo_rows = (a.WA + bm - 2) / a.WA + 3;
-  const int hpix = a.halo_rows * WP;
-  a.halo_bytes = (uint32_t)((hpix + 7) / 8) * 1024;
-  a.n_cb = a.CA / 64;
-  const int bstage = 2 * bn * 128 + 128;
-  const bool wide = bm == 256 && bn == 256;  // 8-wave tile: one block per CU regardless
-  const int cap2 = wide ? 160 * 1024 : 80 * 1024;
-  if (a.n_cb > 1 && 2 * (int)a.halo_bytes + bstage <= cap2) a.halo_nbuf = 2;
-  else if ((int)a.halo_bytes + bstage <= 160 * 1024) a.halo_nbuf = 1;
-  else return false;
-  a.div_hw2 = make_fastdiv((uint32_t)WP);
-  a.div_ha = make_fastdiv((uint32_t)a.HA);
-  return true;
-}
+// ---------------------------------------------------------------- NT launch plan
+// Every NT launch is planned once, by plan_nt(): the introspection (conv_nt_tile), the BN
+// partial-buffer sizes (conv_nt_group_rows), the halo sizing and the dispatcher all read the NtPlan
+// record, so they cannot disagree.  A new tile is added to plan_nt() (and gets its NtTile row).
+constexpr int NT_PLAIN = 0;  // igemm_nt_kernel, per-tap A tiles
+constexpr int NT_QUAD = 1;   // igemm_ntq_kernel, quadrant-phased
+constexpr int NT_HALO = 2;   // igemm_nt_kernel, A staged once as the halo of the tile's image rows
+struct NtQuery {
+  int M, Nout, kg_bytes;  // GEMM rows and columns, bytes of a B row
+  int op = OP_BF16;       // operand type
+  bool c64 = true;        // C64 loader (whole 128-byte K-steps per tap), else the generic one
+  bool c8 = false;        // generic loader on the stem's 8-channel source
+  int epi = EPI_PLAIN;
+  bool halo = false;      // the conv has the halo shape (halo_shape(), bf16 C64 only)
+};
+struct NtPlan {
+  int family;  // NT_PLAIN / NT_QUAD / NT_HALO
+  int bm, bn;  // the tile that runs; bm is also the row group of the epilogues' BN partials
+  bool k32;    // K32 ring (NT_PLAIN, bf16) instead of the 2-stage K64 main loop
+  int stages;
+};
+
+// Test hook (conv_nt_force): pin the K32 / K64 main loop of every NT launch, or disable the
+// 128x256 short-K tile or the 256x256 tile, so tests can compare the policy's alternatives bit
+// for bit.  -1: policy.
+static int g_force_k32 = -1, g_force_mid = -1, g_force_wide = -1;
+void conv_nt_force(int k32, int mid, int wide) { g_force_k32 = k32; g_force_mid = mid; g_force_wide = wide; }
 
 // K-step per NT launch: K32 ring (4 stages; 5 on the 8-wave tile, 160 KB) or K64 double buffer.
 // Measured on MI355X (r2x, bench_conv.py, batch 256): the K32 ring's earlier first MFMA and
@@ -1623,14 +1618,9 @@ static bool setup_halo(NtArgs& a, int R, int S, int tap_stride, int pad) {
 // 256->64 117 -> 103, and the 64-channel dgrads -- while every long-K conv loses 5-20% to the
 // doubled barriers and fragment-read restarts (256x14x14 3x3 68 -> 79 us).  Policy: K32 for
 // M >= 786432 on forward (stats epilogue) GEMMs and 64-column dgrads.
-// Test hook (conv_nt_force): pin the K32 / K64 main loop of every NT launch, or disable the
-// 128x256 short-K tile, so tests can compare the policy's alternatives bit for bit.  -1: policy.
-static int g_force_k32 = -1, g_force_mid = -1, g_force_wide = -1;
-void conv_nt_force(int k32, int mid, int wide) { g_force_k32 = k32; g_force_mid = mid; g_force_wide = wide; }
-
-static bool nt_k32(const NtArgs& a, int epi) {
+static bool nt_k32(const NtQuery& q) {
   if (g_force_k32 >= 0) return g_force_k32 == 1;
-  return a.M >= 786432 && (epi == EPI_STATS || a.Nout <= 64);
+  return q.M >= 786432 && (q.epi == EPI_STATS || q.Nout <= 64);
 }
 
 // Tile policy.  Per K-step a BMxBN tile issues (BM+BN)/8 1-KiB LDS-DMA instructions and reads
@@ -1658,77 +1648,101 @@ static bool use_mid_tile(int M, int Nout, int kg_bytes) {
   return M > 8192 && Nout % 256 == 0 && kg_bytes <= 2 * kmax;
 }
 
-// Tile choice: output channels 64 -> tall 256x64 tile (more M rows per block); small M -> short
-// 64x128 tile; short-K with Nout % 256 == 0 -> 128x256 (use_mid_tile); big GEMMs -> 256x256, else
-// 128x128.  Returns the tile's BM, which is also the row
-// group of the BN partials the STATS / BNB epilogues write (one per workgroup row tile): hosts
-// size those buffers with it, dispatch_nt picks its tile with it -- one definition for both.
-int conv_nt_group_rows(int M, int Nout, int kg_bytes) {
-  if (Nout <= 64) return 256;
-  // small M takes the short 64x128 tile (enough blocks) -- unless the 256x256 grid alone fills the
-  // chip: a 4096^3 GEMM (M = 4096) ran the 64x128 tile at 642 TF/s (VERDICT r3 weak #2 measured
-  // that tile, not the 256x256 one)
-  if (M <= 8192 && !use_wide_tile(M, Nout, kg_bytes)) return 64;
-  if (use_mid_tile(M, Nout, kg_bytes)) return 128;
-  return use_wide_tile(M, Nout, kg_bytes) ? 256 : 128;
+static NtPlan plan_nt(const NtQuery& q) {
+  NtPlan p{};
+  const bool bf16 = q.op == OP_BF16;
+  const bool halo = q.halo && bf16 && q.c64;
+  const bool k32ok = q.c64 || !q.c8;  // the 8-channel (stem) loader packs 8 taps per K64 step
+  // Tile: output channels <= 64 -> tall 256x64 (more M rows per block).  Small M -> short 64x128
+  // (enough blocks) -- unless the 256x256 grid alone fills the chip: a 4096^3 GEMM (M = 4096) ran
+  // the 64x128 tile at 642 TF/s.  Short K with Nout % 256 == 0 -> 128x256 (use_mid_tile); big
+  // GEMMs -> 256x256 (use_wide_tile), else 128x128.
+  const bool wide = use_wide_tile(q.M, q.Nout, q.kg_bytes);
+  if (q.Nout <= 64) { p.bm = 256; p.bn = 64; }
+  else if (q.M <= 8192 && !wide) { p.bm = 64; p.bn = 128; }
+  else if (use_mid_tile(q.M, q.Nout, q.kg_bytes)) { p.bm = 128; p.bn = 256; }
+  else if (wide) { p.bm = 256; p.bn = 256; }
+  else { p.bm = 128; p.bn = 128; }
+  // The 128x256 tile exists as the bf16 per-tap K32 kernel only (fewer instantiations): fp8
+  // operands, halo staging and the stem's 8-channel loader run 128x128 where the rule above says
+  // 128x256 -- the same 128-row groups, so the BN partial buffers are the same either way.
+  if (p.bm == 128 && p.bn == 256 && (!bf16 || halo || !k32ok)) p.bn = 128;
+  const bool mid = p.bm == 128 && p.bn == 256;
+  if (halo) p.family = NT_HALO;
+  else if (bf16 && q.c64 && p.bm == p.bn) p.family = NT_QUAD;  // 256x256 and 128x128
+  else p.family = NT_PLAIN;
+  // fp8 runs the 2-stage pipeline only (fewer instantiations); the 128x256 tile is always K32
+  p.k32 = p.family == NT_PLAIN && bf16 && (mid || (k32ok && nt_k32(q)));
+  with_nt_tile(p.bm, p.bn, [&](auto tile) { p.stages = p.k32 ? decltype(tile)::RING : 2; });
+  return p;
 }
 
-// Introspection for tests: (BM, BN) of the bf16 NT tile dispatch_nt runs for a GEMM of M rows,
-// Nout columns and a B-row length of kg_bytes (fp8 uses the same rule on its byte length).
+int conv_nt_group_rows(int M, int Nout, int kg_bytes) { return plan_nt({M, Nout, kg_bytes}).bm; }
+
 void conv_nt_tile(int M, int Nout, int kg_bytes, int* bm, int* bn) {
-  const int rows = conv_nt_group_rows(M, Nout, kg_bytes);
-  if (Nout <= 64) { *bm = 256; *bn = 64; }
-  else if (rows == 64) { *bm = 64; *bn = 128; }
-  else if (rows == 256) { *bm = 256; *bn = 256; }
-  else if (use_mid_tile(M, Nout, kg_bytes)) { *bm = 128; *bn = 256; }
-  else { *bm = 128; *bn = 128; }
+  const NtPlan p = plan_nt({M, Nout, kg_bytes});
+  *bm = p.bm;
+  *bn = p.bn;
 }
 
+// Halo staging applies to 3x3 / stride 1 / pad 1 convolutions with a same-size output whose A
+// operand has CA = 64 channels (fwd: CA = C, dgrad: CA = K).
+// Measured on MI355X (r2p/r2q, bench_conv.py, batch 256): halo staging pays where one channel
+// block covers the whole reduction (C = 64, ResNet layer1: fwd 114 -> 103 us, dgrad 111 -> 98,
+// BN-fused dgrad 140 -> 130); with several channel blocks the halo reload per block stalls
+// (128x28x28: 86 -> 93 us, 512x7x7: 75 -> 88), so those keep the per-tap A tiles.
+static bool halo_shape(const ConvShape& s, int CA) {
+  return s.R == 3 && s.S == 3 && s.stride == 1 && s.pad == 1 && s.Ho == s.H && s.Wo == s.W && CA == 64;
+}
+
+// Fills the halo fields of `a` for the planned tile; false where the halo does not fit in LDS.
+static bool setup_halo(NtArgs& a, const NtPlan& p) {
+  const int WP = a.WA + 2;
+  const int halo_rows = (a.WA + p.bm - 2) / a.WA + 3;
+  const int hpix = halo_rows * WP;
+  a.halo_bytes = (uint32_t)((hpix + 7) / 8) * 1024;
+  a.n_cb = a.CA / 64;
+  const int bstage = 2 * p.bn * 128 + 128;
+  const bool wide = p.bm == 256 && p.bn == 256;  // 8-wave tile: one block per CU regardless
+  const int cap2 = wide ? 160 * 1024 : 80 * 1024;
+  if (a.n_cb > 1 && 2 * (int)a.halo_bytes + bstage <= cap2) a.halo_nbuf = 2;
+  else if ((int)a.halo_bytes + bstage <= 160 * 1024) a.halo_nbuf = 1;
+  else return false;
+  a.halo_rows = halo_rows;
+  a.div_hw2 = make_fastdiv((uint32_t)WP);
+  a.div_ha = make_fastdiv((uint32_t)a.HA);
+  return true;
+}
+
+// Plan the launch and map the plan to its instantiation.  `halo`: the conv has the halo shape.
 template <bool C64, int EPI, int OP = OP_BF16>
-static void dispatch_nt(const NtArgs& a, hipStream_t st) {
-  const int rows = conv_nt_group_rows(a.M, a.Nout, a.Kg * (OP == OP_BF16 ? 2 : 1));
-  if constexpr (C64 && OP == OP_BF16) {
-    if (a.halo_rows > 0) {
-      if (a.Nout <= 64) run_nt_halo<4, 1, 4, 4, EPI>(a, st);
-      else if (rows == 64) run_nt_halo<2, 2, 2, 4, EPI>(a, st);
-      else if (rows == 256) run_nt_halo<4, 2, 4, 8, EPI>(a, st);
-      else run_nt_halo<2, 2, 4, 4, EPI>(a, st);
-      return;
+static void dispatch_nt(NtArgs& a, bool halo, hipStream_t st) {
+  NtQuery q{a.M, a.Nout, a.Kg * (OP == OP_BF16 ? 2 : 1), OP, C64, a.c8 != 0, EPI, halo};
+  NtPlan p = plan_nt(q);
+  if (p.family == NT_HALO && !setup_halo(a, p)) {  // too wide an image: per-tap A tiles
+    q.halo = false;
+    p = plan_nt(q);
+  }
+  with_nt_tile(p.bm, p.bn, [&](auto tile) {
+    using T = decltype(tile);
+    if constexpr (C64 && OP == OP_BF16) {
+      if (p.family == NT_HALO) {
+        if constexpr (T::K64) return run_nt_halo<T, EPI>(a, st);
+      } else if (p.family == NT_QUAD) {
+        if constexpr (T::QWM > 0) return run_ntq<T, EPI>(a, st);
+      }
     }
-  }
-  if constexpr (OP != OP_BF16) {  // fp8: 2-stage pipeline only (fewer instantiations)
-    if (a.Nout <= 64) run_nt<4, 1, 4, 4, 2, C64, EPI, OP>(a, st);
-    else if (rows == 64) run_nt<2, 2, 2, 4, 2, C64, EPI, OP>(a, st);
-    else if (rows == 256) run_nt<4, 2, 4, 8, 2, C64, EPI, OP>(a, st);
-    else run_nt<2, 2, 4, 4, 2, C64, EPI, OP>(a, st);
-    return;
-  }
-  if constexpr (C64 && OP == OP_BF16) {
-    if (rows == 256 && a.Nout > 64) {  // (Nout <= 64 is the 256x64 tile)
-      run_ntq<2, 4, 4, 2, EPI>(a, st);
-      return;
+    // (the operand type is tested at run time: an fp8 dispatcher goes on instantiating the bf16
+    // kernels of its loader and epilogue, as it always has, so the code object keeps its kernels)
+    if (p.family == NT_PLAIN && q.op != OP_BF16) {
+      if constexpr (T::K64) return run_nt<T, 2, C64, EPI, OP>(a, st);
+    } else if (p.family == NT_PLAIN && p.k32) {
+      return run_nt<T, T::RING, C64, EPI, OP_BF16, true>(a, st);
+    } else if (p.family == NT_PLAIN) {
+      if constexpr (T::K64) return run_nt<T, 2, C64, EPI, OP_BF16>(a, st);
     }
-    if (rows == 128 && a.Nout > 64 && !use_mid_tile(a.M, a.Nout, a.Kg * 2)) {
-      run_ntq<2, 2, 2, 2, EPI>(a, st);
-      return;
-    }
-  }
-  const bool k32ok = C64 || !a.c8;  // the 8-channel (stem) loader packs 8 taps per K64 step
-  if (a.Nout <= 64) {
-    if (k32ok && nt_k32(a, EPI)) run_nt<4, 1, 4, 4, 4, C64, EPI, OP_BF16, true>(a, st);  // 256 x 64
-    else run_nt<4, 1, 4, 4, 2, C64, EPI>(a, st);
-  } else if (rows == 64) {
-    if (k32ok && nt_k32(a, EPI)) run_nt<2, 2, 2, 4, 4, C64, EPI, OP_BF16, true>(a, st);  // 64 x 128
-    else run_nt<2, 2, 2, 4, 2, C64, EPI>(a, st);
-  } else if (rows == 256) {
-    if (k32ok && nt_k32(a, EPI)) run_nt<4, 2, 4, 8, 5, C64, EPI, OP_BF16, true>(a, st);  // 256 x 256
-    else run_nt<4, 2, 4, 8, 2, C64, EPI>(a, st);
-  } else if (k32ok && use_mid_tile(a.M, a.Nout, a.Kg * 2)) {
-    run_nt<2, 2, 4, 8, 3, C64, EPI, OP_BF16, true>(a, st);  // 128 x 256, K32 ring, 2 blocks / CU
-  } else {
-    if (k32ok && nt_k32(a, EPI)) run_nt<2, 2, 4, 4, 4, C64, EPI, OP_BF16, true>(a, st);  // 128 x 128
-    else run_nt<2, 2, 4, 4, 2, C64, EPI>(a, st);
-  }
+    throw std::logic_error("dispatch_nt: no kernel for the planned launch");
+  });
 }
 
 static void fill_common(NtArgs& a, int Mi, int Mj) {
@@ -1740,13 +1754,16 @@ static void fill_common(NtArgs& a, int Mi, int Mj) {
   a.div_s = make_fastdiv((uint32_t)a.S);
 }
 
-void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part,
-                     const ConvShape& s, hipStream_t st, const BnFwdFuse* bn) {
+template <int OP>
+static void conv_fwd_impl(const void* x, const void* w, const float* oscale, const float* ascale, uint16_t* y,
+                          float* part, const ConvShape& s, hipStream_t st, const BnFwdFuse* bn) {
+  constexpr int EB = OP == OP_BF16 ? 2 : 1;
   NtArgs a{};
-  a.a = x; a.b = w; a.out = y; a.part = part;
+  a.a = reinterpret_cast<const uint16_t*>(x); a.b = reinterpret_cast<const uint16_t*>(w);
+  a.out = y; a.part = part; a.oscale = oscale; a.ascale = ascale;
   if (bn != nullptr) { a.sacc = bn->acc; a.part = nullptr; }
-  a.a_bytes = (uint32_t)((int64_t)s.N * s.H * s.W * s.C * 2);
-  a.b_bytes = (uint32_t)((int64_t)s.K * s.R * s.S * s.C * 2);
+  a.a_bytes = (uint32_t)((int64_t)s.N * s.H * s.W * s.C * EB);
+  a.b_bytes = (uint32_t)((int64_t)s.K * s.R * s.S * s.C * EB);
   a.o_bytes = (uint32_t)((int64_t)s.N * s.Ho * s.Wo * s.K * 2);
   a.HA = s.H; a.WA = s.W; a.CA = s.C;
   a.Nout = s.K; a.Kg = s.R * s.S * s.C; a.S = s.S;
@@ -1758,52 +1775,34 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* p
   a.tnr = s.R; a.tns = s.S; a.ntaps = s.R * s.S;
   a.tr0 = 0; a.ts0 = 0; a.tstep = 1;
   a.dr0 = 0; a.ds0 = 0; a.dstep = 1;
-  bool c64 = (s.C % 64) == 0 && s.R * s.S <= 32;  // C64 loader: tap validity bitmask per row
-  if (c64 && s.sw() == s.stride && s.Ho == s.H && s.Wo == s.W) setup_halo(a, s.R, s.S, s.stride, s.pad);
-  if (!c64 && s.C == 8 && 8 % s.S == 0) {
+  // C64 loader: input channels fill whole 128-byte K-steps (64 bf16 / 128 fp8), tap validity
+  // bitmask per row
+  const bool c64 = s.C % (128 / EB) == 0 && s.R * s.S <= 32;
+  const bool halo = OP == OP_BF16 && c64 && s.sw() == 1 && halo_shape(s, s.C);
+  if (OP == OP_BF16 && !c64 && s.C == 8 && 8 % s.S == 0) {  // the stem's super-pixel image
     a.c8 = 1;
     a.c8_rows = 8 / s.S;
     a.c8_step = a.c8_rows * s.W * 8 * 2;
   }
   if (part || bn) {
-    if (c64) dispatch_nt<true, EPI_STATS>(a, st);
-    else dispatch_nt<false, EPI_STATS>(a, st);
+    if (c64) dispatch_nt<true, EPI_STATS, OP>(a, halo, st);
+    else dispatch_nt<false, EPI_STATS, OP>(a, halo, st);
   } else {
-    if (c64) dispatch_nt<true, EPI_PLAIN>(a, st);
-    else dispatch_nt<false, EPI_PLAIN>(a, st);
+    if (c64) dispatch_nt<true, EPI_PLAIN, OP>(a, halo, st);
+    else dispatch_nt<false, EPI_PLAIN, OP>(a, halo, st);
   }
   if (bn != nullptr) launch_bn_finalize_sums(*bn, a.M, s.K, st);
+}
+
+void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part,
+                     const ConvShape& s, hipStream_t st, const BnFwdFuse* bn) {
+  conv_fwd_impl<OP_BF16>(x, w, nullptr, nullptr, y, part, s, st, bn);
 }
 
 void launch_conv_fwd_fp8(const uint8_t* x, const uint8_t* w, const float* oscale, const float* ascale,
                          uint16_t* y, float* part, const ConvShape& s, hipStream_t st, const BnFwdFuse* bn) {
   if (s.C % 16 != 0) throw std::runtime_error("conv_fwd_fp8: input channels must be a multiple of 16");
-  NtArgs a{};
-  a.a = reinterpret_cast<const uint16_t*>(x); a.b = reinterpret_cast<const uint16_t*>(w);
-  a.out = y; a.part = part; a.oscale = oscale; a.ascale = ascale;
-  if (bn != nullptr) { a.sacc = bn->acc; a.part = nullptr; }
-  a.a_bytes = (uint32_t)((int64_t)s.N * s.H * s.W * s.C);
-  a.b_bytes = (uint32_t)((int64_t)s.K * s.R * s.S * s.C);
-  a.o_bytes = (uint32_t)((int64_t)s.N * s.Ho * s.Wo * s.K * 2);
-  a.HA = s.H; a.WA = s.W; a.CA = s.C;
-  a.Nout = s.K; a.Kg = s.R * s.S * s.C; a.S = s.S;
-  a.M = s.N * s.Ho * s.Wo;
-  fill_common(a, s.Ho, s.Wo);
-  a.ash = s.stride; a.asw = s.sw(); a.aoff_h = -s.pad; a.aoff_w = -s.pad;
-  a.OH = s.Ho; a.OW = s.Wo; a.osh = 1; a.osw = 1; a.oph = 0; a.opw = 0;
-  a.dense = 1;
-  a.tnr = s.R; a.tns = s.S; a.ntaps = s.R * s.S;
-  a.tr0 = 0; a.ts0 = 0; a.tstep = 1;
-  a.dr0 = 0; a.ds0 = 0; a.dstep = 1;
-  const bool c128 = (s.C % 128) == 0 && s.R * s.S <= 32;
-  if (part || bn) {
-    if (c128) dispatch_nt<true, EPI_STATS, OP_F8_E4M3>(a, st);
-    else dispatch_nt<false, EPI_STATS, OP_F8_E4M3>(a, st);
-  } else {
-    if (c128) dispatch_nt<true, EPI_PLAIN, OP_F8_E4M3>(a, st);
-    else dispatch_nt<false, EPI_PLAIN, OP_F8_E4M3>(a, st);
-  }
-  if (bn != nullptr) launch_bn_finalize_sums(*bn, a.M, s.K, st);
+  conv_fwd_impl<OP_F8_E4M3>(x, w, oscale, ascale, y, part, s, st, bn);
 }
 
 static int dgrad_class_rows(const ConvShape& s, int ph, int pw) {
@@ -1869,7 +1868,7 @@ static void conv_dgrad_impl(const void* dy, const void* wt, const float* oscale,
       a.tnr = r0 < s.R ? (s.R - r0 + str - 1) / str : 0;
       a.tns = s0 < s.S ? (s.S - s0 + str - 1) / str : 0;
       a.ntaps = a.tnr * a.tns;  // 0 -> kernel writes zeros for this class
-      if (OP == OP_BF16 && str == 1 && s.H == s.Ho && s.W == s.Wo) setup_halo(a, s.R, s.S, 1, s.pad);
+      const bool halo = OP == OP_BF16 && halo_shape(s, s.K);
       if (a.ntaps > 32) throw std::runtime_error("conv_dgrad: more than 32 taps per parity class");
       a.tr0 = r0; a.ts0 = s0; a.tstep = str;
       a.dr0 = (ph + s.pad - r0) / str; a.ds0 = (pw + s.pad - s0) / str; a.dstep = -1;
@@ -1890,14 +1889,14 @@ static void conv_dgrad_impl(const void* dy, const void* wt, const float* oscale,
         a.bn_mask = bn->mask; a.bn_group0 = group0;
         group0 += ceil_div(a.M, conv_nt_group_rows(a.M, a.Nout, a.Kg * EB));
         if constexpr (OP != OP_BF16) {
-          if (!full) { dispatch_nt<false, EPI_BNB, OP>(a, st); continue; }
+          if (!full) { dispatch_nt<false, EPI_BNB, OP>(a, halo, st); continue; }
         }
-        dispatch_nt<true, EPI_BNB, OP>(a, st);
+        dispatch_nt<true, EPI_BNB, OP>(a, halo, st);
       } else {
         if constexpr (OP != OP_BF16) {
-          if (!full) { dispatch_nt<false, EPI_PLAIN, OP>(a, st); continue; }
+          if (!full) { dispatch_nt<false, EPI_PLAIN, OP>(a, halo, st); continue; }
         }
-        dispatch_nt<true, EPI_PLAIN, OP>(a, st);
+        dispatch_nt<true, EPI_PLAIN, OP>(a, halo, st);
       }
     }
 }
@@ -1915,7 +1914,7 @@ void launch_conv_dgrad_fp8(const uint8_t* dy, const uint8_t* wt, const float* os
 }
 
 // ------------------------------------------------------------------- wgrad (bf16: wgrad.hip)
-// fp8 weight gradient (igemm_tn_f8_kernel): split-K planned like plan_wgrad with 128-pixel steps
+// fp8 weight gradient (igemm_tn_f8_kernel): split-K planned like plan_wg (wgrad.hip) with 128-pixel steps
 void conv_wgrad_fp8_plan(const ConvShape& s, int out[4]) {
   const int bmg = s.K % 128 == 0 ? 128 : 64;
   const int ncols = s.R * s.S * s.C;
@@ -1954,22 +1953,17 @@ void launch_conv_wgrad_fp8(const uint8_t* dy8, const uint8_t* x8, const float* d
   const bool pw = s.R == 1 && s.S == 1 && s.stride == 1 && s.sw() == 1 && s.pad == 0 && s.H == s.Ho && s.W == s.Wo;
   const int grid = pl[1] * pl[2];
   const int smem = 2 * (128 * pl[0] + 128 * 128);
-  static bool attr_set[4] = {false, false, false, false};
-  const int which = (pl[0] == 128 ? 0 : 2) + (pw ? 0 : 1);
-  const void* fn = pl[0] == 128 ? (pw ? (const void*)igemm_tn_f8_kernel<128, true> : (const void*)igemm_tn_f8_kernel<128, false>)
-                                : (pw ? (const void*)igemm_tn_f8_kernel<64, true> : (const void*)igemm_tn_f8_kernel<64, false>);
-  if (!attr_set[which]) {
-    hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set[which] = true;
-  }
-  if (pl[0] == 128) {
-    if (pw) hipLaunchKernelGGL((igemm_tn_f8_kernel<128, true>), dim3(grid), dim3(256), smem, st, a);
-    else hipLaunchKernelGGL((igemm_tn_f8_kernel<128, false>), dim3(grid), dim3(256), smem, st, a);
-  } else {
-    if (pw) hipLaunchKernelGGL((igemm_tn_f8_kernel<64, true>), dim3(grid), dim3(256), smem, st, a);
-    else hipLaunchKernelGGL((igemm_tn_f8_kernel<64, false>), dim3(grid), dim3(256), smem, st, a);
-  }
-  check_launch("igemm_tn_f8");
+  // the <BMG, PW> instantiation, selected once
+  auto run = [&](auto bmg, auto pwc) {
+    launch_lds<igemm_tn_f8_kernel<decltype(bmg)::value, decltype(pwc)::value>>("igemm_tn_f8", grid, 256, smem, smem,
+                                                                               st, a);
+  };
+  auto with_pw = [&](auto bmg) {
+    if (pw) run(bmg, std::true_type{});
+    else run(bmg, std::false_type{});
+  };
+  if (pl[0] == 128) with_pw(std::integral_constant<int, 128>{});
+  else with_pw(std::integral_constant<int, 64>{});
 }
 
 }  // namespace pdt

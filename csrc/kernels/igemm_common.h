@@ -1,10 +1,34 @@
-// Shared device helpers of the implicit-GEMM kernels (conv_igemm.hip: forward / input gradient,
-// wgrad.hip: weight gradient): fast division, XCD-aware block remap, LDS-DMA staging and counted
-// waits, the MFMA wrapper and the transposing-read LDS images.
+// Shared helpers of the implicit-GEMM kernels (conv_igemm.hip: forward / input gradient,
+// wgrad.hip: weight gradient): the host-side launch with dynamic LDS, and on the device fast
+// division, XCD-aware block remap, LDS-DMA staging and counted waits, the MFMA wrapper and the
+// transposing-read LDS images.
 #pragma once
 #include "common.h"
 
+#include <stdexcept>
+#include <string>
+
 namespace pdt {
+
+// ------------------------------------------------------------------ launching
+static void check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// Launch KFN with `smem` bytes of dynamic LDS.  Its first launch in the process raises the kernel's
+// dynamic-LDS limit to smem_max, the most any of its launches asks for (one process drives one
+// GPU, so once per kernel is once per device).
+template <auto KFN, class Args>
+static void launch_lds(const char* what, int grid, int block, int smem_max, int smem, hipStream_t st, const Args& a) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, smem_max);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KFN, dim3(grid), dim3(block), smem, st, a);
+  check_launch(what);
+}
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));

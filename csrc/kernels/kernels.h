@@ -61,15 +61,18 @@ struct ConvShape {
   int stride_w = 0;    // horizontal stride when different from `stride` (fwd and wgrad only)
   int sw() const { return stride_w > 0 ? stride_w : stride; }
 };
-// y[N,Ho,Wo,K] = conv(x, w[K][R][S][C]); if part != nullptr also writes per-group
-// BN partials part[ceil(M/G)][2][K] = (sum, M2 about the group mean), G = conv_nt_group_rows(M, K,
-// R*S*C*elem_bytes) = the BM of the workgroup tile the launch uses (one group per row tile).
+// Every fwd / dgrad (NT) launch is planned once (conv_igemm.hip plan_nt); these two read that plan.
+// conv_nt_group_rows: the BM of the workgroup tile a GEMM of M rows, Nout columns and kg_bytes bytes
+// per B row runs, which is also the row group G of the BN partials its epilogue writes (one group
+// per row tile).  The same for bf16 and fp8 operands (pass the row length in bytes of the type).
 int conv_nt_group_rows(int M, int Nout, int kg_bytes);
-// (BM, BN) of the NT workgroup tile the fwd / dgrad launch of such a GEMM runs (test introspection)
+// (BM, BN) of that tile, for tests.  There is no operand-type argument: the answer is for bf16
+// operands on the C64 loader.  Where it says 128x256, an fp8 launch (and the stem's 8-channel
+// loader) runs 128x128 -- the 128x256 tile has bf16 K32 kernels only -- with the same 128-row groups.
 void conv_nt_tile(int M, int Nout, int kg_bytes, int* bm, int* bn);
-// tests: force the NT main loop (k32 1 / 0) and disable the 128x256 tile (mid 0); -1 = policy
+// tests: force the NT main loop (k32 1 / 0), disable the 128x256 tile (mid 0) or the 256x256 tile
+// (wide 0); -1 = policy
 void conv_nt_force(int k32, int mid, int wide = -1);
-// number of stream-K NT launches so far in this process (tests: which path ran)
 // PDT_NT_TIMING builds (scripts/build_variant.sh): per-workgroup phase timestamps of NT launches
 // (s_memtime at start / first operands in LDS / main loop done / epilogue stats done / end, plus
 // s_memrealtime and the CU id), 8 values per block id, copied into `host`; other builds return 0.
@@ -89,6 +92,9 @@ struct BnFwdFuse {
   float momentum, eps;
 };
 void launch_bn_finalize_sums(const BnFwdFuse& bn, int M, int K, hipStream_t st);
+// y[N,Ho,Wo,K] = conv(x, w[K][R][S][C]); if part != nullptr also writes per-group BN partials
+// part[ceil(M/G)][2][K] = (sum, M2 about the group mean), G = conv_nt_group_rows(M, K, R*S*C*2);
+// bn != nullptr: the fp64-totals statistics above instead of `part`
 void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part,
                      const ConvShape& s, hipStream_t st, const BnFwdFuse* bn = nullptr);
 // dx[N,H,W,C] = dgrad(dy[N,Ho,Wo,K], wt[C][R][S][K]) (+ addend[N,H,W,C] if non-null);
@@ -113,8 +119,6 @@ struct BnBwdFuse {
   float* acc2 = nullptr;
 };
 int conv_dgrad_bn_groups(const ConvShape& s, int elem_bytes = 2);
-// addend_sub = 2: addend is a compact [N, ceil(H/2), ceil(W/2), C] map added at even (h, w) only
-// (the input gradient of a 1x1/s2 projection shortcut, computed as a dense 1x1 dgrad)
 // BN backward folded into a 1x1 / stride-1 input gradient (ops/fused.py, last unit of a
 // bottleneck): with dy = k1*g + a*y + b per output channel k (the BN-backward apply written out) and
 // y = W z (the conv's own output), dx = W^T diag(k1) g + (W^T diag(a) W) z + W^T b -- one GEMM over
@@ -126,9 +130,8 @@ struct DgradFold {
   const float* bias;   // [Nout] fp32
 };
 // wfold[C][K + C] bf16 and bias[C] fp32 (followed by 2K floats of scratch) of a DgradFold for the
-// 1x1 conv with transposed bf16
-// weights wt[C][K], BN statistics stats[4][K] (mean, invstd, ...), gamma[K] and backward sums
-// sums[2][K] (sum g, sum g*(y - mean)) over M rows
+// 1x1 conv with transposed bf16 weights wt[C][K], BN statistics stats[4][K] (mean, invstd, ...),
+// gamma[K] and backward sums sums[2][K] (sum g, sum g*(y - mean)) over M rows
 int64_t bn_fold_weights_ws_floats(int C, int K);  // bias + coefficient / partials scratch
 void launch_bn_fold_weights(const uint16_t* wt, const float* stats, const float* gamma, const float* sums,
                             int M, int C, int K, uint16_t* wfold, float* bias, hipStream_t st);
@@ -140,6 +143,8 @@ void launch_bn_fold_wgrad(float* t1, float* gram, const float* colsum, const uin
                           const float* stats, const float* gamma, const float* sums, int M, int C, int K,
                           float* out, float* dgamma, float* dbeta, int* done, bool zero_sums, hipStream_t st,
                           int csum_slots = 1);  // bn_csum_slots(): bn_act_fwd's [slots][C], re-zeroed here
+// addend_sub = 2: addend is a compact [N, ceil(H/2), ceil(W/2), C] map added at even (h, w) only
+// (the input gradient of a 1x1/s2 projection shortcut, computed as a dense 1x1 dgrad)
 void launch_conv_dgrad(const uint16_t* dy, const uint16_t* wt, uint16_t* dx, const uint16_t* addend,
                        const ConvShape& s, hipStream_t st, const BnBwdFuse* bn = nullptr,
                        int addend_sub = 0, const DgradFold* fold = nullptr);
@@ -151,13 +156,13 @@ void conv_wgrad_plan(const ConvShape& s, bool deterministic, int out[4]);
 // CUs the weight-gradient split-K plan leaves free for collective kernels (0: plan the whole chip)
 void conv_wgrad_set_cu_reserve(int n);
 int conv_wgrad_cu_reserve();
-// accumulate: dw += wgrad (autograd accumulation semantics; lets the block write straight into
-// the flat gradient buffer), else dw = wgrad.
 // fp8 weight gradient: dw[K][R][S][C] (+)= wgrad(dy8 e5m2 [N,Ho,Wo,K] * dy_deq, x8 e4m3 [N,H,W,C] * x_deq),
 // fp32 atomics (non-deterministic order); C % 16 == 0, K % 64 == 0.  plan: (bmg, tiles, splits, steps/split)
 void conv_wgrad_fp8_plan(const ConvShape& s, int out[4]);
 void launch_conv_wgrad_fp8(const uint8_t* dy8, const uint8_t* x8, const float* dy_deq, const float* x_deq,
                            float* dw, const ConvShape& s, bool accumulate, hipStream_t st);
+// accumulate: dw += wgrad (autograd accumulation semantics; lets the block write straight into
+// the flat gradient buffer), else dw = wgrad.
 // zero / zero_n: optional fp32 buffer the weight-gradient kernel clears (workgroup 0) -- the BN-sum
 // accumulator whose consumer is ordered before this launch (ops/fused.py _BN_ACC)
 void launch_conv_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* ws,
@@ -201,12 +206,12 @@ void launch_bn_act_bwd_reduce(const uint16_t* dz, const uint16_t* z, const uint1
                               float* sums, float* dgamma, float* dbeta, hipStream_t st);
 // dy = gamma*invstd*(g - sum_g/M - (y-mean)*sum_gx*invstd^2/M) (training) or gamma*invstd*g;
 // dres = g (if non-null)
+// dgamma/dbeta (optional): += sums[1]*invstd, += sums[0] (the BN parameter gradients, for sums
+// accumulated by the producing dgrad's epilogue atomics -- BnBwdFuse::acc)
 void launch_bn_act_bwd_apply(const uint16_t* dz, const uint16_t* z, const uint16_t* y,
                              const float* stats, const float* gamma, const float* sums, int mask,
                              bool training, int64_t M, int K, uint16_t* dy, uint16_t* dres,
                              hipStream_t st, float* dgamma = nullptr, float* dbeta = nullptr);
-// dgamma/dbeta (optional): += sums[1]*invstd, += sums[0] (the BN parameter gradients, for sums
-// accumulated by the producing dgrad's epilogue atomics -- BnBwdFuse::acc)
 
 // Stem BN + ReLU + 3x3/s2/p1 max pool fused (bn_act.hip): out/idx as maxpool_fwd of the ReLU'd
 // bf16 z, which is never written.  Backward: the BN reduction / apply with dz gathered from the

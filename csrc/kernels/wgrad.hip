@@ -655,11 +655,6 @@ __global__ void __launch_bounds__(256) wg_splitk_reduce_kernel(const float4* __r
 }
 
 // ------------------------------------------------------------------------------------- host
-static void wg_check(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
 // Kernel family of a weight gradient: KIND_GEN (wgrad_kernel, any conv) or KIND_HALO3 (3x3/s1/p1).
 constexpr int KIND_GEN = 0, KIND_HALO3 = 1;
 
@@ -788,27 +783,13 @@ size_t conv_wgrad_ws_floats(const ConvShape& s, bool deterministic) {
 template <int WM, int WN, bool PW>
 static void run_wg(const WgArgs& a, int nb, hipStream_t st) {
   using CFG = WgCfg<WM, WN>;
-  auto kfn = wgrad_kernel<WM, WN, PW>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, CFG::SMEM);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3(nb), dim3(CFG::NT), CFG::SMEM, st, a);
-  wg_check("wgrad_kernel");
+  launch_lds<wgrad_kernel<WM, WN, PW>>("wgrad_kernel", nb, CFG::NT, CFG::SMEM, CFG::SMEM, st, a);
 }
 
 template <int WM, int WC, int TC>
 static void run_wh(const WhArgs& a, int nb, hipStream_t st) {
   using CFG = WhCfg<WM, WC, TC>;
-  auto kfn = wgrad_halo3_kernel<WM, WC, TC>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, CFG::SMEM);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kfn, dim3(nb), dim3(512), CFG::SMEM, st, a);
-  wg_check("wgrad_halo3_kernel");
+  launch_lds<wgrad_halo3_kernel<WM, WC, TC>>("wgrad_halo3_kernel", nb, 512, CFG::SMEM, CFG::SMEM, st, a);
 }
 
 void launch_conv_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* ws,
@@ -874,7 +855,7 @@ void launch_conv_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* 
     hipLaunchKernelGGL(wg_splitk_reduce_kernel, dim3((unsigned)((n4 + 15) / 16)), dim3(256), 0, st,
                        reinterpret_cast<const float4*>(ws), p.splits, n4, reinterpret_cast<float4*>(dw),
                        accumulate ? 1 : 0);
-    wg_check("splitk_reduce");
+    check_launch("splitk_reduce");
   }
 }
 

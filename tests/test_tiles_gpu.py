@@ -1,7 +1,7 @@
 """Every implicit-GEMM tile configuration the ResNet-50 bench runs, checked against fp32 PyTorch.
 
 ``test_kernels_gpu.py`` covers the conv kernels on small shapes; the tile policy
-(``conv_nt_group_rows`` / ``plan_wgrad`` in ``csrc/kernels/conv_igemm.hip``) only selects the
+(``plan_nt`` in ``csrc/kernels/conv_igemm.hip``, ``plan_wg`` in ``csrc/kernels/wgrad.hip``) only selects the
 256x256 NT tile for GEMMs with >= 196 row tiles, which no small shape reaches.  Here each test
 asserts WHICH tile ran (``conv_nt_tile`` / ``conv_wgrad_plan`` introspection) and compares the
 kernel with an fp32 reference of the same op:
