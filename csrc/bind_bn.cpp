@@ -149,7 +149,7 @@ std::tuple<Tensor, Tensor> bn_act_bwd_apply(const Tensor& dz, const Tensor& z, c
                                             const Tensor& sums, int64_t mask, bool training,
                                             bool want_dres, const std::optional<Tensor>& dgamma,
                                             const std::optional<Tensor>& dbeta) {
-  auto b = bn_bwd_prologue(dz, y, stats, mask, z);
+  auto b = bn_bwd_prologue(dz, y, stats, mask, z, /*pow2_groups=*/false);
   auto pg = bn_param_sinks(dgamma, dbeta, b.K);
   c10::hip::HIPGuard g(dz.get_device());
   auto dy = at::empty_like(dz);

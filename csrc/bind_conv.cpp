@@ -213,7 +213,7 @@ std::tuple<Tensor, Tensor> dgrad_bn_core(const Tensor& dy_like, const pdt::ConvS
                                          const std::optional<Tensor>& z_in, const Tensor& stats, int64_t mask,
                                          const std::optional<Tensor>& dgamma,
                                          const std::optional<Tensor>& dbeta, const std::optional<Tensor>& acc_in,
-                                         const SecondBn& bn2, Launch&& launch) {
+                                         const SecondBn& bn2, Launch&& launch, int fold_k = 0) {
   check_bf16_nhwc(y, "y");
   TORCH_CHECK(y.size(0) == s.N && y.size(1) == s.H && y.size(2) == s.W && y.size(3) == s.C,
               "dgrad_bn: y must have the shape of x");
@@ -260,7 +260,7 @@ std::tuple<Tensor, Tensor> dgrad_bn_core(const Tensor& dy_like, const pdt::ConvS
     launch(s, bf(dx), a.ptr, &bn, st, a.layout);
     return {dx, acc->view({2, s.C})};
   }
-  const int G = pdt::conv_dgrad_bn_groups(s, (int)dy_like.element_size());
+  const int G = pdt::conv_dgrad_bn_groups(s, (int)dy_like.element_size(), fold_k);
   // sums, partials and the reduction workspace as slices of ONE allocation (host issue: each
   // caching-allocator call is ~1-2 us, and this binding runs once per BatchNorm per step)
   const int64_t n_sums = 2 * (int64_t)s.C, n_part = (int64_t)G * 2 * s.C;
@@ -320,7 +320,8 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn_fold(const Tensor& g, const Tensor& z_i
                        [&](const pdt::ConvShape& sh, uint16_t* dx, const uint16_t* ap, const pdt::BnBwdFuse* bn,
                            hipStream_t st, int asub) {
                          pdt::launch_conv_dgrad(cbf(g), cbf(wfold), dx, ap, sh, st, bn, asub, &fold);
-                       });
+                       },
+                       /*fold_k=*/C);  // the partials are sized for the GEMM over K + C
 }
 
 // fp8 dgrad operands: dy8 e5m2 NHWC [N,Ho,Wo,K], wt8 e4m3 [C,R,S,K] with per-C scale wscale,

@@ -202,12 +202,14 @@ struct BnBwd {
   const uint16_t* z;
 };
 
+// pow2_groups: the reduce and the fp8 apply keep one 8-channel group per thread only when K / 8
+// divides 256; the bf16 apply rounds its grid to a multiple of K / 8 (ew_blocks) and takes any K % 8 == 0
 inline BnBwd bn_bwd_prologue(const Tensor& dz, const Tensor& y, const Tensor& stats, int64_t mask,
-                             const Tensor& z) {
+                             const Tensor& z, bool pow2_groups = true) {
   check_bf16_nhwc(dz, "dz");
   check_bf16_nhwc(y, "y");
   const int K = y.size(3);
-  TORCH_CHECK(256 % (K / 8) == 0, "bn backward: channels must divide 2048 and be a power of two");
+  TORCH_CHECK(!pow2_groups || 256 % (K / 8) == 0, "bn backward: channels must divide 2048 and be a power of two");
   check_stats(stats, K);
   if (mask == 1) check_bf16_nhwc(z, "z");
   return {K, y.numel() / K, mask == 1 ? cbf(z) : nullptr};

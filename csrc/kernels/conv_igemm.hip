@@ -1812,12 +1812,14 @@ static int dgrad_class_rows(const ConvShape& s, int ph, int pw) {
   return (Mi <= 0 || Mj <= 0) ? 0 : s.N * Mi * Mj;
 }
 
-int conv_dgrad_bn_groups(const ConvShape& s, int elem_bytes) {
+int conv_dgrad_bn_groups(const ConvShape& s, int elem_bytes, int fold_k) {
+  // the B row of the launch this sizes the partials for: a DgradFold appends fold_k elements to it
+  // (conv_dgrad_impl: Kg += CA2), and the tile -- so the row group -- depends on its length
   int g = 0;
   for (int ph = 0; ph < s.stride; ++ph)
     for (int pw = 0; pw < s.stride; ++pw) {
       const int M = dgrad_class_rows(s, ph, pw);
-      if (M > 0) g += ceil_div(M, conv_nt_group_rows(M, s.C, s.R * s.S * s.K * elem_bytes));
+      if (M > 0) g += ceil_div(M, conv_nt_group_rows(M, s.C, (s.R * s.S * s.K + fold_k) * elem_bytes));
     }
   return g;
 }

@@ -118,7 +118,7 @@ struct BnBwdFuse {
   const float* stats2 = nullptr;
   float* acc2 = nullptr;
 };
-int conv_dgrad_bn_groups(const ConvShape& s, int elem_bytes = 2);
+int conv_dgrad_bn_groups(const ConvShape& s, int elem_bytes = 2, int fold_k = 0);  // fold_k: DgradFold::CA2
 // BN backward folded into a 1x1 / stride-1 input gradient (ops/fused.py, last unit of a
 // bottleneck): with dy = k1*g + a*y + b per output channel k (the BN-backward apply written out) and
 // y = W z (the conv's own output), dx = W^T diag(k1) g + (W^T diag(a) W) z + W^T b -- one GEMM over

@@ -6,7 +6,8 @@ final bf16 rounding of outputs.
 
 The conv tests' whole-tensor norm ratio cannot see a localized error (a zeroed GEMM row measures
 0.008 at two of CONV_SHAPES and passes): tests/test_conv_exact_gpu.py pins the same kernels bit for
-bit on integer operands, tile by tile and loader by loader.
+bit on integer operands, tile by tile and loader by loader; tests/test_bn_head_exact_gpu.py does the
+same for the BN, pooling, folded-BN and head kernels on crafted coefficients.
 """
 import pytest
 import torch
