@@ -14,7 +14,9 @@
   ``build/native_mix`` (the public surface of ``_C`` is pinned, and other tools link every object of
   ``build/native`` into ``_C``);
 * ``csrc/img/*`` (the resampling input transform) likewise, into a third module ``_C_img<EXT_SUFFIX>``
-  with its objects in ``build/native_img``;
+  with its objects in ``build/native_img``, except the augmentation-policy kernel
+  (``csrc/img/autoaug.hip``), whose object is kept in ``build/native_aug`` (the object list of
+  ``build/native_img`` is pinned by the tests of the resampling transform);
 * ``csrc/ema/*`` (the weight-EMA update) likewise, into a fourth module ``_C_ema<EXT_SUFFIX>`` with
   its objects in ``build/native_ema``.
 
@@ -46,6 +48,7 @@ BUILD = os.path.join(ROOT, "build", "native")
 BUILD_MIX = os.path.join(ROOT, "build", "native_mix")
 BUILD_IMG = os.path.join(ROOT, "build", "native_img")
 BUILD_EMA = os.path.join(ROOT, "build", "native_ema")
+BUILD_AUG = os.path.join(ROOT, "build", "native_aug")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -106,9 +109,12 @@ def asan_ema_out_path() -> str:
 
 
 def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc, tdir, force, jobs, verbose,
-                  sanitize):
-    """Compile the stale objects of one extension module into ``bdir`` and link them into ``so``."""
-    os.makedirs(bdir, exist_ok=True)
+                  sanitize, side_dirs=None):
+    """Compile the stale objects of one extension module into ``bdir`` and link them into ``so``.
+    ``side_dirs`` maps a source to another object directory for its object alone."""
+    side_dirs = side_dirs or {}
+    for d in [bdir] + list(side_dirs.values()):
+        os.makedirs(d, exist_ok=True)
     py_inc = sysconfig.get_paths()["include"]
     host_flags = common + [f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-DUSE_ROCM=1", f"-DTORCH_EXTENSION_NAME={name}",
                            "-DTORCH_API_INCLUDE_EXTENSION_H", "-I", py_inc, "-I", CSRC,
@@ -118,7 +124,7 @@ def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc,
     objs = []
     for src in kern_srcs + host_srcs:
         rel = os.path.relpath(src, CSRC).replace(os.sep, "_")
-        obj = os.path.join(bdir, rel + ".o")
+        obj = os.path.join(side_dirs.get(src, bdir), rel + ".o")
         objs.append(obj)
         stale = force or not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), hdr_t)
         if not stale:
@@ -138,8 +144,9 @@ def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc,
                 f.result()
                 if verbose:
                     print(f"[build_native]   ok {os.path.relpath(futs[f], ROOT)}", flush=True)
-    for old in set(glob.glob(os.path.join(bdir, "*.o"))) - set(objs):
-        os.remove(old)  # its source was removed or renamed
+    for d in [bdir] + list(side_dirs.values()):
+        for old in set(glob.glob(os.path.join(d, "*.o"))) - set(objs):
+            os.remove(old)  # its source was removed or renamed
     os.makedirs(os.path.dirname(so), exist_ok=True)
     if force or jobs_list or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(o) for o in objs):
         tlib = os.path.join(tdir, "lib")
@@ -173,11 +180,14 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                   sorted(glob.glob(os.path.join(CSRC, "mix", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_mix_asan") if sanitize else BUILD_MIX,
                   asan_mix_out_path() if sanitize else mix_out_path(), [], *rest)
-    # the resampling input transform: the same arrangement
+    # the resampling input transform and the augmentation policy: the same arrangement, the policy
+    # kernel's object in a directory of its own
+    aug_dir = os.path.join(ROOT, "build", "native_aug_asan") if sanitize else BUILD_AUG
     _build_module("_C_img", sorted(glob.glob(os.path.join(CSRC, "img", "*.hip"))),
                   sorted(glob.glob(os.path.join(CSRC, "img", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_img_asan") if sanitize else BUILD_IMG,
-                  asan_img_out_path() if sanitize else img_out_path(), [], *rest)
+                  asan_img_out_path() if sanitize else img_out_path(), [], *rest,
+                  side_dirs={os.path.join(CSRC, "img", "autoaug.hip"): aug_dir})
     # the weight-EMA update: the same arrangement
     _build_module("_C_ema", sorted(glob.glob(os.path.join(CSRC, "ema", "*.hip"))),
                   sorted(glob.glob(os.path.join(CSRC, "ema", "*.cpp"))),

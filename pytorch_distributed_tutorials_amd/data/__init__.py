@@ -1,3 +1,11 @@
+from .autoaug import (  # noqa: F401
+    AugConfig,
+    AugDraw,
+    apply_policy,
+    apply_policy_levels,
+    draw_policy,
+    erase_boxes,
+)
 from .datasets import (  # noqa: F401
     CIFAR_MEAN,
     CIFAR_STD,

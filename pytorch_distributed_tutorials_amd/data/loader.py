@@ -18,6 +18,12 @@ sample (``RandomResizedCrop`` for training, ``CenterCropResize`` for evaluation)
 output size, flipped and normalized -- one ``_C_img.resized_crop`` kernel on the GPU
 (``csrc/img/resample.hip``), ``resized_crop`` of ``data/resize.py`` otherwise, both fed by the same
 box and flip draws.
+
+With ``aug=`` the batch goes through the per-sample augmentation policy of ``data/autoaug.py``
+(TrivialAugmentWide, RandomErasing) between the crop chain and normalisation: the crop kernel runs with
+normalisation off and one ``_C_img.autoaug`` op (``csrc/img/autoaug.hip``) applies the policy,
+normalises and erases on the GPU, ``apply_policy`` of ``data/autoaug.py`` otherwise, both fed by the same
+``draw_policy`` draws.  Order: crop + flip, policy, normalise, erase, mix.
 """
 from __future__ import annotations
 
@@ -27,6 +33,7 @@ from typing import Iterator, Optional, Sequence, Tuple, Union
 import torch
 import torch.nn.functional as F
 
+from .autoaug import MAX_SIDE, AugConfig, AugDraw, apply_policy, draw_policy
 from .datasets import TensorImageDataset
 from .mix import MixConfig, MixDraw, MixedTarget, draw_mix, mix_batch
 from .resize import CenterCropResize, RandomResizedCrop, center_box, draw_rrc, resized_crop
@@ -71,13 +78,22 @@ class DeviceLoader:
     implies) by a random box resized to the transform's size and a flip;
     ``transform=CenterCropResize(...)`` is the evaluation counterpart (no draws, ``augment`` must be
     off).  Batches then have the transform's output size, and mix boxes are drawn for that size and
-    applied (``mix_batch``) to the transformed batch on both paths.  ``None`` changes nothing."""
+    applied (``mix_batch``) to the transformed batch on both paths.  ``None`` changes nothing.
+
+    ``aug=AugConfig(...)`` runs the per-sample policy of ``data/autoaug.py`` on the training batch: after
+    crop and flip the batch is quantised to 8-bit levels, every sample goes through its own operation,
+    then normalisation, the erase box and the mix (``mix_batch`` on both paths).  It needs a training
+    chain (``augment=True`` or a ``RandomResizedCrop``) over an un-normalised 3-channel dataset.  Its
+    draws come from a third random stream, after the batch's crop/flip draws: a run with the policy
+    sees the crops, flips and mixes of the run without it.  ``None`` (or a config with everything
+    off) changes nothing."""
 
     def __init__(self, dataset: TensorImageDataset, batch_size: int, sampler=None,
                  shuffle: bool = False, augment: bool = False, device="cpu",
                  drop_last: bool = False, seed: int = 0, fused: Optional[bool] = None,
                  mix: Optional[MixConfig] = None,
-                 transform: Union[RandomResizedCrop, CenterCropResize, None] = None):
+                 transform: Union[RandomResizedCrop, CenterCropResize, None] = None,
+                 aug: Optional[AugConfig] = None):
         self.ds = dataset.to(device)
         # MixUp / CutMix (data/mix.py): batches come as (images, MixedTarget); None = hard labels
         self.mix = MixConfig(*mix).validate() if mix is not None else None
@@ -103,6 +119,22 @@ class DeviceLoader:
         # size of the batches (the 16-byte stores of the fused kernels need a width that is a multiple of 4)
         self.out_hw = tuple(self.ds.images.shape[2:]) if transform is None else transform.out_hw
         self.fused = bool(fused) and self.device.type == "cuda" and self.out_hw[1] % 4 == 0
+        # the per-sample policy (data/autoaug.py); None = off
+        aug = AugConfig(*aug).validate() if aug is not None else None
+        self.aug = aug if aug is not None and aug.enabled else None
+        if self.aug is not None:
+            if isinstance(transform, CenterCropResize):
+                raise ValueError("aug: the augmentation policy cannot follow CenterCropResize, an evaluation transform")
+            if not augment and transform is None:
+                raise ValueError("aug: the augmentation policy is a training transform: it needs augment=True or a "
+                                 "RandomResizedCrop (evaluation never augments)")
+            if self.ds.normalized:
+                raise ValueError("aug: the augmentation policy works on 8-bit levels: it needs an un-normalised "
+                                 "uint8 dataset (cifar10, array), not a normalised one")
+            if self.ds.images.shape[1] != 3:
+                raise ValueError(f"aug: the augmentation policy needs RGB images, got C = {self.ds.images.shape[1]}")
+            if max(self.out_hw) > MAX_SIDE:
+                raise ValueError(f"aug: the augmentation policy takes sides up to {MAX_SIDE}, got {self.out_hw}")
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -135,6 +167,12 @@ class DeviceLoader:
             # and flips the same run without mixing sees
             mgen = torch.Generator(device=self.device)
             mgen.manual_seed((self.seed * 1000003 + self.epoch) ^ 0x4D6978)
+        agen = None
+        if self.aug is not None:
+            # the third stream: the policy draws of a batch come after its crop/flip draws and advance
+            # neither that stream nor the mix stream
+            agen = torch.Generator(device=self.device)
+            agen.manual_seed((self.seed * 1000003 + self.epoch) ^ 0x417567)
         idx = idx.to(self.device)
         n = idx.numel()
         stop = (n // self.batch_size) * self.batch_size if self.drop_last else n
@@ -142,7 +180,7 @@ class DeviceLoader:
             bi = idx[s:s + self.batch_size]
             y = self.ds.labels.index_select(0, bi)
             if self.fused:
-                x, draw = self._fused_batch(bi, gen, mgen)
+                x, draw = self._fused_batch(bi, gen, mgen, agen)
                 yield x, self._target(y, draw)
                 continue
             x = self.ds.images.index_select(0, bi)
@@ -150,14 +188,14 @@ class DeviceLoader:
                 box, flip = self._draw_transform(bi.numel(), gen)
                 x = x.float()
                 if not self.ds.normalized:
-                    x = _normalize(resized_crop(x.div_(255.0), box, self.out_hw, flip), self.ds.mean, self.ds.std)
+                    x = self._finish(resized_crop(x.div_(255.0), box, self.out_hw, flip), agen)
                 else:
                     x = resized_crop(x, box, self.out_hw, flip)
             elif not self.ds.normalized:
                 x = x.float().div_(255.0)
                 if self.augment:
                     x = random_crop_flip(x, 4, gen)
-                x = _normalize(x, self.ds.mean, self.ds.std)
+                x = self._finish(x, agen)
             elif self.augment:
                 x = random_crop_flip(x, 4, gen)
             x = x.float().contiguous()
@@ -165,6 +203,25 @@ class DeviceLoader:
             if draw is not None:
                 x = mix_batch(x, draw.partner, draw.w, draw.box)
             yield x, self._target(y, draw)
+
+    def _draw_aug(self, b: int, gen) -> AugDraw:
+        return draw_policy(b, *self.out_hw, self.aug, device=self.device, gen=gen)
+
+    def _finish(self, x: torch.Tensor, agen) -> torch.Tensor:
+        """The torch path from the cropped ``[0, 1]`` batch on: the policy when there is one (it
+        normalises and erases as well), the normalisation alone otherwise."""
+        if self.aug is None:
+            return _normalize(x, self.ds.mean, self.ds.std)
+        return apply_policy(x, self._draw_aug(x.shape[0], agen), self.ds.mean, self.ds.std)
+
+    def _fused_aug(self, x: torch.Tensor, agen) -> torch.Tensor:
+        """The fused path's counterpart of ``_finish`` for a policy: one ``_C_img.autoaug`` op."""
+        from ..ops._ext import native_img
+        d = self._draw_aug(x.shape[0], agen)
+        # erasing alone: every operation is Identity, so the statistics pass has nothing to do
+        passes = 2 if self.aug.policy == "none" else 3
+        return native_img().autoaug(x, d.op, d.param, d.matrix, d.erase, True, list(self.ds.mean),
+                                    list(self.ds.std), passes)
 
     def _draw_mix(self, b: int, gen) -> Optional[MixDraw]:
         if self.mix is None:
@@ -186,16 +243,20 @@ class DeviceLoader:
             return y
         return MixedTarget(y, y.index_select(0, draw.partner), draw.lam)
 
-    def _fused_batch(self, bi: torch.Tensor, gen, mgen=None) -> Tuple[torch.Tensor, Optional[MixDraw]]:
+    def _fused_batch(self, bi: torch.Tensor, gen, mgen=None, agen=None) -> Tuple[torch.Tensor, Optional[MixDraw]]:
         from ..ops._ext import native, native_img, native_mix
         b = bi.numel()
+        # with a policy the crop kernel leaves the batch in [0, 1] and autoaug normalises
+        normalize = not self.ds.normalized and self.aug is None
         if self.transform is not None:
             box, flip = self._draw_transform(b, gen)
             imgs = self.ds.images
             if imgs.dtype not in (torch.uint8, torch.float32):
                 imgs = imgs.float()
             x = native_img().resized_crop(imgs.contiguous(), bi.contiguous(), box, flip, *self.out_hw,
-                                          not self.ds.normalized, list(self.ds.mean), list(self.ds.std))
+                                          normalize, list(self.ds.mean), list(self.ds.std))
+            if self.aug is not None:
+                x = self._fused_aug(x, agen)
             draw = self._draw_mix(b, mgen)
             if draw is not None:
                 x = mix_batch(x, draw.partner, draw.w, draw.box)
@@ -210,6 +271,12 @@ class DeviceLoader:
         if imgs.dtype not in (torch.uint8, torch.float32):
             imgs = imgs.float()
         draw = self._draw_mix(b, mgen)
+        if self.aug is not None:
+            x = self._fused_aug(native().augment(imgs.contiguous(), bi.contiguous(), oy, ox, flip, pad, False,
+                                                 list(self.ds.mean), list(self.ds.std)), agen)
+            if draw is not None:
+                x = mix_batch(x, draw.partner, draw.w, draw.box)
+            return x, draw
         if draw is None:
             return native().augment(imgs.contiguous(), bi.contiguous(), oy, ox, flip, pad,
                                     not self.ds.normalized, list(self.ds.mean), list(self.ds.std)), None

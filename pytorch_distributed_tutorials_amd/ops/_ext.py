@@ -7,7 +7,7 @@ and FAILS LOUDLY when it is missing -- there is no silent eager fallback for
 device tensors.  CPU tensors use the PyTorch reference implementations (tests).
 
 The MixUp / CutMix ops live in a second module of the same build, ``_C_mix*.so``, and the
-resampling input transform in a third, ``_C_img*.so``, and the weight-EMA update in a fourth,
+resampling input transform and the augmentation policy in a third, ``_C_img*.so``, and the weight-EMA update in a fourth,
 ``_C_ema*.so`` (the public surface of ``_C`` is pinned); ``native_mix()``, ``native_img()`` and
 ``native_ema()`` load them under the same rules.
 """

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .data import (CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
+from .data import (AugConfig, CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
                    build_dataset)
 from .models import build_model
 from .optim import LARS, SGD, ModelEma, WarmupPolyLR
@@ -137,6 +137,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval-transform", default="none", choices=["none", "center-crop"],
                    help="center-crop: evaluate on the centred --eval-crop-pct box resized to --train-size")
     p.add_argument("--eval-crop-pct", type=float, default=0.875)
+    # ---- per-sample augmentation policy (off by default): after crop + flip, before normalisation
+    p.add_argument("--auto-augment", default="none", choices=["none", "trivial-wide"],
+                   help="trivial-wide: TrivialAugmentWide, one of 14 operations per sample at a random magnitude "
+                        "(un-normalised uint8 datasets: cifar10, array)")
+    p.add_argument("--random-erase-prob", type=float, default=0.0,
+                   help="RandomErasing: probability that a box of the normalised sample is zeroed; 0 = off")
+    p.add_argument("--random-erase-scale", type=float, nargs=2, default=[0.02, 0.33], metavar=("LO", "HI"),
+                   help="RandomErasing: range of the box area as a share of the image")
+    p.add_argument("--random-erase-ratio", type=float, nargs=2, default=[0.3, 3.3], metavar=("LO", "HI"),
+                   help="RandomErasing: range of the box aspect h / w (log-uniform)")
     # ---- weight EMA (off by default): evaluated and checkpointed beside the raw weights
     p.add_argument("--ema-decay", type=float, default=0.0,
                    help="exponential moving average of the weights and BatchNorm statistics with this decay "
@@ -263,6 +273,15 @@ def main(argv: Optional[list] = None) -> int:
         input_transforms(args, (1, 1))
     except ValueError as e:
         raise SystemExit(f"--train-size / --rrc-scale / --rrc-ratio / --eval-crop-pct: {e}")
+    try:
+        aug = AugConfig(args.auto_augment, args.random_erase_prob, tuple(args.random_erase_scale),
+                        tuple(args.random_erase_ratio)).validate()
+    except ValueError as e:
+        raise SystemExit(f"--auto-augment / --random-erase-prob / --random-erase-scale / --random-erase-ratio: {e}")
+    aug = aug if aug.enabled else None
+    if aug is not None and args.data not in ("cifar10", "array"):
+        raise SystemExit(f"--auto-augment / --random-erase-prob cannot be combined with --data {args.data}: the "
+                         "policy works on 8-bit levels and must be given an un-normalised uint8 dataset (cifar10, array)")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema-decay must be in [0, 1) (0 = off), got {args.ema_decay}")
     if args.ema_every < 1:
@@ -367,7 +386,7 @@ def main(argv: Optional[list] = None) -> int:
     _, eval_tf = input_transforms(args, test_set.images.shape[2:])
     train_sampler = DistributedSampler(len(train_set), num_replicas=env.world_size, rank=env.rank)
     train_loader = DeviceLoader(train_set, args.batch_size, sampler=train_sampler, augment=True,
-                                device=device, seed=args.seed + env.rank, mix=mix, transform=train_tf)
+                                device=device, seed=args.seed + env.rank, mix=mix, transform=train_tf, aug=aug)
     test_loader = DeviceLoader(test_set, 128, shuffle=False, augment=False, device=device, transform=eval_tf)
 
     graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1) \
