@@ -552,7 +552,8 @@ def test_weight_mirror_matches_packs(gpu, native_ext):
 
 def test_stem_superpixel_matches_generic(gpu, native_ext):
     """Super-pixel stem (K = 224 implicit GEMM on a re-laid-out image) == channel-padded generic
-    stem (image_to_nhwc + conv_bn): forward output, running stats and parameter gradients."""
+    stem (image_to_nhwc + conv_bn): forward output, running stats and parameter gradients.
+    (Norm ratios only; tests/test_stem_exact_gpu.py pins the stem kernels bit for bit.)"""
     import copy
     from pytorch_distributed_tutorials_amd import ops
     torch.manual_seed(0)
@@ -905,7 +906,9 @@ def test_avgpool_linear_and_ce_autograd(gpu, native_ext):
 def test_stem_halo_conv_vs_fp32(gpu, native_ext, n, h, w):
     """Halo-staged stem forward (csrc/kernels/stem.hip) vs fp32 conv2d on the same bf16-rounded
     image and weights, plus its per-output-row BN partials (sum, M2) vs fp32; the Wo > 128 case
-    falls back to the generic implicit GEMM (row-tile partials)."""
+    falls back to the generic implicit GEMM (row-tile partials).  A norm ratio cannot see one pixel or
+    one row group: tests/test_stem_exact_gpu.py checks y, the row sums and M2 on integer operands for every
+    TM, Ho mod 4, several persistent passes, and that fallback through the (2, 1)-stride shape."""
     C = native_ext
     torch.manual_seed(1)
     x = torch.randn(n, 3, h, w, device=gpu)
@@ -936,7 +939,9 @@ def test_stem_halo_conv_vs_fp32(gpu, native_ext, n, h, w):
 def test_stem_bwd_fused_matches_unfused(gpu, native_ext, n, h, w, det):
     """Fused stem backward (BN/pool apply inside the weight gradient, csrc/kernels/stem.hip) vs the
     unfused pool_bn_bwd_apply + stem_wgrad on identical inputs (same bf16 dy values, different
-    summation order), and vs an fp32 reference weight gradient of the same bf16 dy."""
+    summation order), and vs an fp32 reference weight gradient of the same bf16 dy.  Both references take
+    dy from the unfused kernel; tests/test_stem_exact_gpu.py compares against an fp64 reference of the whole
+    apply + weight gradient with crafted coefficients and argmax maps, bit for bit, at small shapes."""
     C = native_ext
     torch.manual_seed(2)
     x = torch.randn(n, 3, h, w, device=gpu)
