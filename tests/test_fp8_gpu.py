@@ -104,6 +104,8 @@ def test_pack_weight_fp8(gpu, native_ext):
 
 
 def test_quant_e4m3_delayed_scaling(gpu, native_ext):
+    """Two slots on random data.  The three-slot rotation, the cleared next slot, the scale's
+    power-of-two boundaries and clamps, and the codes byte for byte: test_opt_exact_gpu.py."""
     C = native_ext
     g = torch.Generator().manual_seed(6)
     x = (torch.randn(2, 4, 4, 32, generator=g) * 3).to(torch.bfloat16).to(gpu)

@@ -309,6 +309,9 @@ def test_softmax_xent_and_top1(gpu, native_ext):
 
 @pytest.mark.parametrize("nesterov", [False, True])
 def test_sgd_flat(gpu, native_ext, nesterov):
+    """A smoke-level check on random data (one size, dampening 0, grad_scale 1, 8 ulp).  The bit-exact
+    cases -- every variant, the tail and grid-stride sizes, the bf16 mirror -- are in
+    test_opt_exact_gpu.py::test_sgd_step_exact."""
     C = native_ext
     n = 10001
     p = torch.randn(n, device=gpu)
@@ -512,7 +515,9 @@ def test_block_handoff_with_extra_consumer(gpu, native_ext):
 
 def test_weight_mirror_matches_packs(gpu, native_ext):
     """The bf16 conv-weight mirror (written by the fused SGD step + one batched transpose) equals
-    the per-layer packs bit for bit, and is refreshed after a torch in-place weight update."""
+    the per-layer packs bit for bit, and is refreshed after a torch in-place weight update.  The packs
+    themselves, the batched transpose and the mirror write are held to independent references in
+    test_opt_exact_gpu.py (pack_weight*, pack_t_batched, sgd_step / lars_update mirrors)."""
     from pytorch_distributed_tutorials_amd import ops
     from pytorch_distributed_tutorials_amd.models import build_model
     from pytorch_distributed_tutorials_amd.optim import SGD

@@ -1,7 +1,9 @@
 """Fused LARS (``csrc/kernels/lars.hip``, ``optim.LARS``) and label smoothing in the fused softmax
 cross entropy, on the GPU.  The oracle throughout is ``ops.reference.lars_momentum_`` /
 ``lars_trust_ratio`` (float64 norms) and ``torch.nn.functional.cross_entropy``; tolerances are the
-ones ``test_sgd_flat`` and ``test_softmax_xent_and_top1`` use."""
+ones ``test_sgd_flat`` and ``test_softmax_xent_and_top1`` use.  The three passes on crafted inputs --
+exact partial sums, trust ratios of perfect-square norms, the update with written trust values,
+dampening, segment sub-ranges -- are in ``test_opt_exact_gpu.py``, bit for bit."""
 import copy
 
 import pytest
