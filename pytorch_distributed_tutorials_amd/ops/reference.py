@@ -204,3 +204,42 @@ def lars_momentum_(params, grads, bufs, lr: float, momentum: float, dampening: f
         if trust != 1.0:
             d = d * trust
         sgd_momentum_([p], [d], [b], lr, momentum, dampening, 0.0, nesterov, first_step)
+
+
+def lamb_(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999,
+          eps: float = 1e-6, weight_decay: float = 0.0, trust: bool = True, exclude_1d: bool = True):
+    """LAMB (You et al. 2020) on lists of tensors, update number ``step = 1, 2, ...``; returns the
+    trust ratio of every tensor.  Per tensor, with ``bc1 = 1 - beta1**step`` and
+    ``bc2 = 1 - beta2**step`` in float64 (a float32 tensor rounds them, and ``sqrt(bc2)``, to float32)::
+
+        m = beta1*m + (1-beta1)*g ;  v = beta2*v + (1-beta2)*g*g
+        a = (m/bc1) / (sqrt(v)/sqrt(bc2) + eps)                 # torch.optim.Adam's form
+        u = a + wd_eff*p                                        # wd_eff = 0 for an excluded tensor
+        ratio = float32(|p| / |u|), norms from float64 sums of squares;
+                1 if excluded, or trust is off, or |p| == 0, or |u| == 0
+        p = p - lr*ratio*u
+
+    ``exclude_1d``: tensors with ``ndim <= 1`` get neither weight decay nor the ratio, as in
+    ``lars_momentum_``.  ``trust=False`` is AdamW (with ``exclude_1d=False``, ``torch.optim.AdamW`` in
+    exact arithmetic).  No gradient-norm clipping and no clamp of the ratio."""
+    if step < 1:
+        raise ValueError(f"lamb_: update numbers start at 1, got {step}")
+    bc1 = 1.0 - beta1 ** step
+    sbc2 = (1.0 - beta2 ** step) ** 0.5
+    ratios = []
+    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
+        excluded = bool(exclude_1d and p.ndim <= 1)
+        m.mul_(beta1).add_(g, alpha=1 - beta1)
+        v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+        u = (m / bc1) / (v.sqrt() / sbc2 + eps)
+        if weight_decay != 0 and not excluded:
+            u = u.add(p, alpha=weight_decay)
+        ratio = 1.0
+        if trust and not excluded:
+            pn = float(p.detach().double().pow(2).sum().sqrt())
+            un = float(u.double().pow(2).sum().sqrt())
+            if pn != 0 and un != 0:
+                ratio = float(torch.tensor(pn / un, dtype=torch.float64).float())
+        p.add_(u, alpha=-lr * ratio)
+        ratios.append(ratio)
+    return ratios

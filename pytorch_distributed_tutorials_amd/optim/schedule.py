@@ -44,3 +44,32 @@ class WarmupPolyLR:
             for group in self.optimizer.param_groups:
                 group["lr"] = lr
         return lr
+
+
+class WarmupCosineLR:
+    """Linear warm-up, then half a cosine: the schedule of the LAMB / AdamW recipes.  Stateless like
+    ``WarmupPolyLR``, with the same warm-up and the same ``set(step)`` contract:
+
+    * warm-up, ``step < warmup_steps``: ``base_lr * (step + 1) / warmup_steps``;
+    * decay: ``end_lr + (base_lr - end_lr) * (1 + cos(pi * t)) / 2`` with
+      ``t = (step - warmup_steps) / (total_steps - warmup_steps)`` clamped to [0, 1], so the first
+      decay step runs at ``base_lr`` and every step from ``total_steps`` on at ``end_lr``.
+    """
+
+    def __init__(self, optimizer, base_lr: float, warmup_steps: int, total_steps: int, end_lr: float = 0.0):
+        if warmup_steps < 0 or total_steps < 1 or warmup_steps > total_steps:
+            raise ValueError(f"need 0 <= warmup_steps <= total_steps and total_steps >= 1, got "
+                             f"{warmup_steps}, {total_steps}")
+        self.optimizer = optimizer
+        self.base_lr, self.end_lr = float(base_lr), float(end_lr)
+        self.warmup_steps, self.total_steps = int(warmup_steps), int(total_steps)
+
+    def lr_at(self, step: int) -> float:
+        import math
+        if step < self.warmup_steps:
+            return self.base_lr * (max(step, 0) + 1) / self.warmup_steps
+        span = self.total_steps - self.warmup_steps
+        t = 1.0 if span <= 0 else min(max((step - self.warmup_steps) / span, 0.0), 1.0)
+        return self.end_lr + (self.base_lr - self.end_lr) * 0.5 * (1.0 + math.cos(math.pi * t))
+
+    set = WarmupPolyLR.set

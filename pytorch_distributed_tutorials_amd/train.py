@@ -30,7 +30,7 @@ from . import ops
 from .data import (AugConfig, CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
                    build_dataset)
 from .models import build_model
-from .optim import LARS, SGD, ModelEma, WarmupPolyLR
+from .optim import LAMB, LARS, SGD, ModelEma, WarmupCosineLR, WarmupPolyLR
 from .parallel import DistributedDataParallel, destroy, init_distributed
 from .parallel.comm import CommOptions
 from .utils.checkpoint import load_checkpoint, save_checkpoint
@@ -101,18 +101,27 @@ def build_parser() -> argparse.ArgumentParser:
                         "the bucketed all-reduces, SGD) in a HIP graph once and replay it for every "
                         "full-size batch; the launch-bound ResNet-18/CIFAR step gains the most")
     # ---- large-batch recipe (the defaults are the reference's plain SGD at a constant rate)
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
-                   help="lars = layer-wise trust ratios on top of SGD with momentum (optim.LARS)")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "lars", "lamb", "adamw"],
+                   help="lars = layer-wise trust ratios on top of SGD with momentum (optim.LARS); lamb = Adam "
+                        "moments, decoupled weight decay and layer-wise trust ratios (optim.LAMB); adamw = the "
+                        "same without the ratios")
     p.add_argument("--momentum", type=float, default=0.9)
     p.add_argument("--weight-decay", type=float, default=1e-5)
     p.add_argument("--trust-coefficient", type=float, default=1e-3, help="LARS eta")
     p.add_argument("--lars-eps", type=float, default=1e-8)
     p.add_argument("--lars-adapt-1d", action="store_true",
                    help="LARS: also decay and adapt BatchNorm parameters and biases (exclude_1d off)")
+    p.add_argument("--beta1", type=float, default=0.9, help="LAMB / AdamW: decay of the first moment")
+    p.add_argument("--beta2", type=float, default=0.999, help="LAMB / AdamW: decay of the second moment")
+    p.add_argument("--adam-eps", type=float, default=1e-6, help="LAMB / AdamW: eps of the denominator")
+    p.add_argument("--lamb-adapt-1d", action="store_true",
+                   help="LAMB / AdamW: also decay (and, for LAMB, adapt) BatchNorm parameters and biases "
+                        "(exclude_1d off)")
     p.add_argument("--label-smoothing", type=float, default=0.0)
-    p.add_argument("--lr-schedule", default="constant", choices=["constant", "warmup-poly"],
+    p.add_argument("--lr-schedule", default="constant", choices=["constant", "warmup-poly", "warmup-cosine"],
                    help="warmup-poly: linear warm-up over --warmup-epochs to --learning_rate, then "
-                        "polynomial (power 2) decay to --lr-end at the end of --num_epochs")
+                        "polynomial (power 2) decay to --lr-end at the end of --num_epochs; warmup-cosine: "
+                        "the same warm-up, then half a cosine down to --lr-end")
     p.add_argument("--warmup-epochs", type=float, default=5.0)
     p.add_argument("--lr-end", type=float, default=0.0)
     # ---- input-side regularisers (off by default): per-sample MixUp / CutMix on the training batch
@@ -260,6 +269,10 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(f"--graph cannot follow --lr-schedule {args.lr_schedule}: the captured step bakes "
                          "the learning rate in, so a schedule would re-capture it every step; use "
                          "--lr-schedule constant with --graph")
+    if not (0.0 <= args.beta1 < 1.0 and 0.0 <= args.beta2 < 1.0):
+        raise SystemExit(f"--beta1 / --beta2 must be in [0, 1), got {args.beta1}, {args.beta2}")
+    if args.adam_eps < 0.0:
+        raise SystemExit(f"--adam-eps must be >= 0, got {args.adam_eps}")
     try:
         mix = MixConfig(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.mix_switch_prob).validate()
     except ValueError as e:
@@ -356,6 +369,11 @@ def main(argv: Optional[list] = None) -> int:
                          weight_decay=args.weight_decay, trust_coefficient=args.trust_coefficient,
                          eps=args.lars_eps, exclude_1d=not args.lars_adapt_1d,
                          overlap=False if args.graph else None)
+    elif args.optimizer in ("lamb", "adamw"):
+        # always the post-backward step (optim/lamb.py): nothing to attach, with or without --graph
+        optimizer = LAMB(ddp_model.parameters(), lr=args.learning_rate, betas=(args.beta1, args.beta2),
+                         eps=args.adam_eps, weight_decay=args.weight_decay, trust=args.optimizer == "lamb",
+                         exclude_1d=not args.lamb_adapt_1d)
     else:
         optimizer = SGD(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
                         weight_decay=args.weight_decay, overlap=False if args.graph else None)
@@ -402,6 +420,11 @@ def main(argv: Optional[list] = None) -> int:
         schedule = WarmupPolyLR(optimizer, args.learning_rate,
                                 min(int(round(args.warmup_epochs * steps_per_epoch)), total), total,
                                 power=2.0, end_lr=args.lr_end)
+    elif args.lr_schedule == "warmup-cosine":
+        total = max(args.num_epochs * steps_per_epoch, 1)
+        schedule = WarmupCosineLR(optimizer, args.learning_rate,
+                                  min(int(round(args.warmup_epochs * steps_per_epoch)), total), total,
+                                  end_lr=args.lr_end)
     done = False
     for epoch in range(start_epoch, args.num_epochs):
         print("Local Rank: {}, Epoch: {}, Training ...".format(local_rank, epoch), flush=True)
