@@ -20,7 +20,9 @@
 * ``csrc/ema/*`` (the weight-EMA update) likewise, into a fourth module ``_C_ema<EXT_SUFFIX>`` with
   its objects in ``build/native_ema``;
 * ``csrc/opt/*`` (the fused LAMB / AdamW step) likewise, into a fifth module ``_C_opt<EXT_SUFFIX>`` with
-  its objects in ``build/native_opt``.
+  its objects in ``build/native_opt``;
+* ``csrc/loss/*`` (the binary cross-entropy loss head) likewise, into a sixth module
+  ``_C_loss<EXT_SUFFIX>`` with its objects in ``build/native_loss``.
 
 Incremental: an object is rebuilt when its source or any header under csrc/ is
 newer, and an object whose source is gone is deleted (other tools link every object of the build
@@ -52,6 +54,7 @@ BUILD_IMG = os.path.join(ROOT, "build", "native_img")
 BUILD_EMA = os.path.join(ROOT, "build", "native_ema")
 BUILD_AUG = os.path.join(ROOT, "build", "native_aug")
 BUILD_OPT = os.path.join(ROOT, "build", "native_opt")
+BUILD_LOSS = os.path.join(ROOT, "build", "native_loss")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -119,6 +122,14 @@ def asan_opt_out_path() -> str:
     return os.path.join(ROOT, "build", "asan", "_C_opt" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 
+def loss_out_path() -> str:
+    return os.path.join(PKG, "_C_loss" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
+def asan_loss_out_path() -> str:
+    return os.path.join(ROOT, "build", "asan", "_C_loss" + sysconfig.get_config_var("EXT_SUFFIX"))
+
+
 def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc, tdir, force, jobs, verbose,
                   sanitize, side_dirs=None):
     """Compile the stale objects of one extension module into ``bdir`` and link them into ``so``.
@@ -174,8 +185,8 @@ def _build_module(name, kern_srcs, host_srcs, bdir, so, libs, common, abi, tinc,
 
 def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool = True,
           sanitize: bool = False) -> str:
-    """Build the extension modules ``_C``, ``_C_mix``, ``_C_img``, ``_C_ema`` and ``_C_opt``; returns the
-    path of ``_C``."""
+    """Build the extension modules ``_C``, ``_C_mix``, ``_C_img``, ``_C_ema``, ``_C_opt`` and ``_C_loss``;
+    returns the path of ``_C``."""
     tdir, tinc, abi = _torch_paths()
     opt = ["-O0", "-g"] if debug else (["-O1", "-g"] + SAN_FLAGS if sanitize else ["-O3"])
     common = ["-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1",
@@ -210,6 +221,11 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                   sorted(glob.glob(os.path.join(CSRC, "opt", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_opt_asan") if sanitize else BUILD_OPT,
                   asan_opt_out_path() if sanitize else opt_out_path(), [], *rest)
+    # the binary cross-entropy loss head: the same arrangement
+    _build_module("_C_loss", sorted(glob.glob(os.path.join(CSRC, "loss", "*.hip"))),
+                  sorted(glob.glob(os.path.join(CSRC, "loss", "*.cpp"))),
+                  os.path.join(ROOT, "build", "native_loss_asan") if sanitize else BUILD_LOSS,
+                  asan_loss_out_path() if sanitize else loss_out_path(), [], *rest)
     return so
 
 

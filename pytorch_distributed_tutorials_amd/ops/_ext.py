@@ -8,9 +8,9 @@ device tensors.  CPU tensors use the PyTorch reference implementations (tests).
 
 The MixUp / CutMix ops live in a second module of the same build, ``_C_mix*.so``, and the
 resampling input transform and the augmentation policy in a third, ``_C_img*.so``, and the weight-EMA update in a fourth,
-``_C_ema*.so``, and the fused LAMB / AdamW step in a fifth, ``_C_opt*.so`` (the public surface of ``_C`` is
-pinned); ``native_mix()``, ``native_img()``, ``native_ema()`` and ``native_opt()`` load them under the same
-rules.
+``_C_ema*.so``, and the fused LAMB / AdamW step in a fifth, ``_C_opt*.so``, and the binary cross-entropy loss
+head in a sixth, ``_C_loss*.so`` (the public surface of ``_C`` is pinned); ``native_mix()``, ``native_img()``,
+``native_ema()``, ``native_opt()`` and ``native_loss()`` load them under the same rules.
 """
 from __future__ import annotations
 
@@ -19,7 +19,7 @@ import importlib.util as importlib_util
 import os
 from typing import Any, Dict, Optional, Tuple
 
-# module name ("_C", "_C_mix", "_C_img", "_C_ema", "_C_opt") -> (module or None, the reason it failed to load or None)
+# module name ("_C", "_C_mix", "_C_img", "_C_ema", "_C_opt", "_C_loss") -> (module or None, the reason it failed to load or None)
 _MODULES: Dict[str, Tuple[Optional[Any], Optional[BaseException]]] = {}
 
 
@@ -79,6 +79,10 @@ def native_opt_available() -> bool:
     return _load("_C_opt")[0] is not None
 
 
+def native_loss_available() -> bool:
+    return _load("_C_loss")[0] is not None
+
+
 def native_mix() -> Any:
     """Return the batch-mixing extension module or raise with the reason it failed to load."""
     return _require("_C_mix")
@@ -97,6 +101,11 @@ def native_ema() -> Any:
 def native_opt() -> Any:
     """Return the LAMB / AdamW extension module or raise with the reason it failed to load."""
     return _require("_C_opt")
+
+
+def native_loss() -> Any:
+    """Return the loss-head extension module or raise with the reason it failed to load."""
+    return _require("_C_loss")
 
 
 def native() -> Any:

@@ -26,7 +26,7 @@ from . import reference as ref
 from . import streams
 from ..data.mix import MixedTarget
 from ..utils.seed import deterministic
-from ._ext import native, native_mix
+from ._ext import native, native_loss, native_mix
 
 _CPU_DTYPE = torch.float32  # activation dtype of the CPU reference path
 # Module switches: the ones tests, scripts or the README's knob table set.
@@ -673,6 +673,67 @@ class CrossEntropyLoss(nn.Module):
         if isinstance(labels, MixedTarget):
             return mix_cross_entropy(logits, labels.labels_a, labels.labels_b, labels.lam, self.label_smoothing)
         return cross_entropy(logits, labels, self.label_smoothing)
+
+
+# ----------------------------------------------------------------------------
+# binary cross entropy with logits -- fused target + fwd + bwd
+# ----------------------------------------------------------------------------
+class _BCEWithLogits(torch.autograd.Function):
+    """Sigmoid cross entropy against the smoothed (and, with ``labels_b`` / ``lam``, mixed) label
+    target, optionally binarised at ``target_threshold`` (negative = off)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_a, labels_b, lam, label_smoothing, target_threshold, sum_classes):
+        if logits.is_cuda:
+            mixed = labels_b is not None
+            loss, dlogits = native_loss().bce_with_logits(
+                logits.float().contiguous(), labels_a.contiguous(), labels_b.contiguous() if mixed else None,
+                lam.float().contiguous() if mixed else None, float(label_smoothing), float(target_threshold),
+                bool(sum_classes))
+        else:
+            loss, dlogits = ref.bce_with_logits(logits, labels_a, labels_b, lam, label_smoothing, target_threshold,
+                                                sum_classes)
+        ctx.save_for_backward(dlogits)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        (dlogits,) = ctx.saved_tensors
+        if dlogits.is_cuda:  # scaled on the device by the (device) loss gradient: no host sync
+            return (native().scale_by(dlogits, dloss.float().reshape(1)),) + (None,) * 6
+        return (dlogits * dloss,) + (None,) * 6
+
+
+def binary_cross_entropy(logits: torch.Tensor, labels, label_smoothing: float = 0.0,
+                         target_threshold: Optional[float] = None, sum_classes: bool = False) -> torch.Tensor:
+    """Binary cross entropy with logits against the one-hot target of ``labels`` (a label tensor or
+    the ``MixedTarget`` of a mixed batch), smoothed by ``label_smoothing`` (on = 1 - s + s / C,
+    off = s / C) and, with ``target_threshold``, binarised to (target > threshold).  Mean over all
+    elements; ``sum_classes`` sums over the classes and averages over the rows."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    if target_threshold is not None and not 0.0 <= target_threshold < 1.0:
+        raise ValueError(f"target_threshold must be in [0, 1), got {target_threshold}")
+    thr = -1.0 if target_threshold is None else float(target_threshold)
+    if isinstance(labels, MixedTarget):
+        return _BCEWithLogits.apply(logits, labels.labels_a, labels.labels_b, labels.lam, label_smoothing, thr,
+                                    sum_classes)
+    return _BCEWithLogits.apply(logits, labels, None, None, label_smoothing, thr, sum_classes)
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """The loss of the "ResNet strikes back" recipe: ``binary_cross_entropy`` with these options; the
+    target is a label tensor or the ``MixedTarget`` of a mixed batch."""
+
+    def __init__(self, label_smoothing: float = 0.0, target_threshold: Optional[float] = None,
+                 sum_classes: bool = False):
+        super().__init__()
+        self.label_smoothing = float(label_smoothing)
+        self.target_threshold = None if target_threshold is None else float(target_threshold)
+        self.sum_classes = bool(sum_classes)
+
+    def forward(self, logits: torch.Tensor, labels) -> torch.Tensor:
+        return binary_cross_entropy(logits, labels, self.label_smoothing, self.target_threshold, self.sum_classes)
 
 
 def top1_correct(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:

@@ -155,6 +155,40 @@ def softmax_xent_mix(logits: torch.Tensor, labels_a: torch.Tensor, labels_b: tor
     return loss, p / n
 
 
+def bce_with_logits(logits: torch.Tensor, labels_a: torch.Tensor, labels_b: Optional[torch.Tensor] = None,
+                    lam: Optional[torch.Tensor] = None, label_smoothing: float = 0.0,
+                    target_threshold: float = -1.0, sum_classes: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Binary cross entropy with logits, every class an independent sigmoid, and its gradient
+    w.r.t. the logits.  The target is the smoothed label vector T_x(c) = on if c == x else off with
+    off = s / C and on = 1 - s + off, blended per row as lam T_a + (1 - lam) T_b when ``labels_b``
+    and ``lam`` are given (T_a alone where a == b), formed in fp32, and binarised to (t > thr) when
+    ``target_threshold`` is not negative.  Mean over all elements, or with ``sum_classes`` the sum
+    over classes and the mean over rows.  With lam == 1 on every row the result is that of the
+    hard-label call bit for bit."""
+    if (labels_b is None) != (lam is None):
+        raise ValueError("labels_b and lam go together")
+    z = logits.float()
+    n, c = z.shape
+    off = label_smoothing / c
+    on = 1.0 - label_smoothing + off
+    cols = torch.arange(c, device=z.device)
+
+    def smoothed(x):
+        return torch.where(cols[None, :] == x[:, None], on, off).to(torch.float32)
+
+    t = smoothed(labels_a)
+    if lam is not None:
+        l = lam.float()[:, None]
+        t = torch.where((labels_a == labels_b)[:, None], t, l * t + (1.0 - l) * smoothed(labels_b))
+    if target_threshold >= 0.0:
+        t = (t > torch.tensor(target_threshold, dtype=torch.float32, device=z.device)).to(torch.float32)
+    scale = 1.0 / n if sum_classes else 1.0 / (n * c)
+    e = torch.exp(-z.abs())
+    loss = (z.clamp_min(0.0) - z * t + torch.log1p(e)).sum() * scale
+    sig = torch.where(z >= 0, torch.ones_like(e), e) / (1.0 + e)
+    return loss, (sig - t) * scale
+
+
 def top1_correct(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return (logits.argmax(1) == labels).sum()
 

@@ -118,6 +118,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="LAMB / AdamW: also decay (and, for LAMB, adapt) BatchNorm parameters and biases "
                         "(exclude_1d off)")
     p.add_argument("--label-smoothing", type=float, default=0.0)
+    p.add_argument("--loss", default="ce", choices=["ce", "bce"],
+                   help="bce: binary cross entropy, every class an independent sigmoid, against the smoothed "
+                        "(and mixed) one-hot target (ops.BCEWithLogitsLoss), the loss of the LAMB recipe")
+    p.add_argument("--bce-target-thresh", type=float, default=None, metavar="T",
+                   help="--loss bce: binarise the target to (target > T), T in [0, 1); default off")
+    p.add_argument("--bce-sum-classes", action="store_true",
+                   help="--loss bce: sum over the classes and average over the batch, not over every element")
     p.add_argument("--lr-schedule", default="constant", choices=["constant", "warmup-poly", "warmup-cosine"],
                    help="warmup-poly: linear warm-up over --warmup-epochs to --learning_rate, then "
                         "polynomial (power 2) decay to --lr-end at the end of --num_epochs; warmup-cosine: "
@@ -297,6 +304,12 @@ def main(argv: Optional[list] = None) -> int:
                          "policy works on 8-bit levels and must be given an un-normalised uint8 dataset (cifar10, array)")
     if not 0.0 <= args.ema_decay < 1.0:
         raise SystemExit(f"--ema-decay must be in [0, 1) (0 = off), got {args.ema_decay}")
+    if args.bce_target_thresh is not None and not 0.0 <= args.bce_target_thresh < 1.0:
+        raise SystemExit(f"--bce-target-thresh must be in [0, 1), got {args.bce_target_thresh}")
+    if args.loss != "bce" and (args.bce_target_thresh is not None or args.bce_sum_classes):
+        raise SystemExit("--bce-target-thresh / --bce-sum-classes need --loss bce")
+    if not 0.0 <= args.label_smoothing <= 1.0 and args.loss == "bce":
+        raise SystemExit(f"--label-smoothing must be in [0, 1], got {args.label_smoothing}")
     if args.ema_every < 1:
         raise SystemExit(f"--ema-every must be at least 1, got {args.ema_every}")
     if args.ema_decay > 0.0 and args.dtype == "fp8":
@@ -351,7 +364,11 @@ def main(argv: Optional[list] = None) -> int:
                                         bucket_cap_mb=args.bucket_mb, wire_dtype=args.wire_dtype,
                                         comm_options=CommOptions.from_env(timeout=args.timeout))
     holder["ddp"] = ddp_model
-    if mix is not None:  # the two-label target: ops.CrossEntropyLoss for both impls (CPU = reference)
+    if args.loss == "bce":  # ops.BCEWithLogitsLoss for both impls, mixed or not (CPU = reference)
+        criterion = ops.BCEWithLogitsLoss(label_smoothing=args.label_smoothing,
+                                          target_threshold=args.bce_target_thresh,
+                                          sum_classes=args.bce_sum_classes)
+    elif mix is not None:  # the two-label target: ops.CrossEntropyLoss for both impls (CPU = reference)
         criterion = ops.CrossEntropyLoss(label_smoothing=args.label_smoothing)
     elif args.label_smoothing != 0.0:
         criterion = ops.CrossEntropyLoss(label_smoothing=args.label_smoothing) if impl == "native" \
