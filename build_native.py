@@ -20,7 +20,9 @@
 * ``csrc/ema/*`` (the weight-EMA update) likewise, into a fourth module ``_C_ema<EXT_SUFFIX>`` with
   its objects in ``build/native_ema``;
 * ``csrc/opt/*`` (the fused LAMB / AdamW step) likewise, into a fifth module ``_C_opt<EXT_SUFFIX>`` with
-  its objects in ``build/native_opt``;
+  its objects in ``build/native_opt``, except the gradient-norm clipping kernels (``csrc/opt/clip.hip``),
+  whose object is kept in ``build/native_clip`` (the object list of ``build/native_opt`` is pinned by
+  the tests of the LAMB step);
 * ``csrc/loss/*`` (the binary cross-entropy loss head) likewise, into a sixth module
   ``_C_loss<EXT_SUFFIX>`` with its objects in ``build/native_loss``.
 
@@ -55,6 +57,7 @@ BUILD_EMA = os.path.join(ROOT, "build", "native_ema")
 BUILD_AUG = os.path.join(ROOT, "build", "native_aug")
 BUILD_OPT = os.path.join(ROOT, "build", "native_opt")
 BUILD_LOSS = os.path.join(ROOT, "build", "native_loss")
+BUILD_CLIP = os.path.join(ROOT, "build", "native_clip")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -216,11 +219,14 @@ def build(force: bool = False, jobs: int = 0, debug: bool = False, verbose: bool
                   sorted(glob.glob(os.path.join(CSRC, "ema", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_ema_asan") if sanitize else BUILD_EMA,
                   asan_ema_out_path() if sanitize else ema_out_path(), [], *rest)
-    # the fused LAMB / AdamW step: the same arrangement
+    # the fused LAMB / AdamW step and the gradient-norm clipping: the same arrangement, the clipping
+    # kernels' object in a directory of its own
+    clip_dir = os.path.join(ROOT, "build", "native_clip_asan") if sanitize else BUILD_CLIP
     _build_module("_C_opt", sorted(glob.glob(os.path.join(CSRC, "opt", "*.hip"))),
                   sorted(glob.glob(os.path.join(CSRC, "opt", "*.cpp"))),
                   os.path.join(ROOT, "build", "native_opt_asan") if sanitize else BUILD_OPT,
-                  asan_opt_out_path() if sanitize else opt_out_path(), [], *rest)
+                  asan_opt_out_path() if sanitize else opt_out_path(), [], *rest,
+                  side_dirs={os.path.join(CSRC, "opt", "clip.hip"): clip_dir})
     # the binary cross-entropy loss head: the same arrangement
     _build_module("_C_loss", sorted(glob.glob(os.path.join(CSRC, "loss", "*.hip"))),
                   sorted(glob.glob(os.path.join(CSRC, "loss", "*.cpp"))),

@@ -29,17 +29,22 @@ struct LambSpace {
   LambRecord* rec;
 };
 
-// fp32 flat buffers of one size, 16-byte aligned; `mirror` (or null) receives bf16(p') per element
+// fp32 flat buffers of one size, 16-byte aligned; `mirror` (or null) receives bf16(p') per element;
+// `clip` (or null) is the clip record of clip.h: pass 1 then takes clip[kClipCoef] * g, rounded to
+// fp32, for g.  The gradient buffer itself is never written.
 struct LambBufs {
   float* p;
   const float* g;
   float* m;
   float* v;
   uint16_t* mirror;
+  const float* clip = nullptr;
 };
 
+// trust_clip: the ratios of pass 2 are clamped at 1 (timm's Lamb(trust_clip=True))
 struct LambHyper {
   double lr, beta1, beta2, eps, wd;
+  bool trust_clip = false;
 };
 
 // Every launcher covers the segments [seg_lo, seg_hi) and throws std::runtime_error on a range
@@ -52,7 +57,7 @@ struct LambHyper {
 void launch_lamb_moments(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,
                          const LambHyper& h, hipStream_t st);
 // pass 2: trust[seg] = excluded or |p| == 0 or |u| == 0 ? 1 : float(|p| / |u|); writes the record's
-// bias corrections and, with `advance`, done <- done + 1
+// bias corrections and, with `advance`, done <- done + 1; with h.trust_clip the ratio is min(ratio, 1)
 void launch_lamb_trust(const LambSpace& sp, int seg_lo, int seg_hi, const LambHyper& h, bool advance,
                        hipStream_t st);
 // pass 3: p -= lr trust[seg] u over the chunks of the segments pass 1 left open (u recomputed from

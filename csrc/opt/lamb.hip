@@ -19,7 +19,11 @@
 // No floating-point atomics; the sum of a chunk (per-thread order, wave butterfly, 4 waves) and of a
 // segment (lane k takes chunks k, k+64, ..., then the butterfly) are fixed by the table alone, so
 // the grid, the stream and the segment range of a launch never change a bit of the result.
+// Gradient-norm clipping (clip.hip): with a clip record the first pass multiplies every gradient
+// element by the record's coefficient as it loads it (one fp32 rounding, what an in-place scale pass
+// would have stored); the gradient buffer itself stays unscaled.  trust_clip clamps the ratio at 1.
 #include "kernels/common.h"
+#include "opt/clip.h"
 #include "opt/lamb.h"
 
 #include <algorithm>
@@ -70,19 +74,22 @@ __device__ __forceinline__ float direction(float p, float m, float v, float wde,
 }
 
 // SINGLE: trust is off, every chunk is finished here and nothing is summed
-template <bool SINGLE, bool MIRROR>
+// CLIP: the gradient is clip[kClipCoef] * g, rounded to fp32, before the moments
+template <bool SINGLE, bool MIRROR, bool CLIP>
 __global__ void __launch_bounds__(256) lamb_moments_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v, Table tb,
                                                            const LambRecord* __restrict__ rec,
                                                            double* __restrict__ partials, int seg_lo, int seg_hi,
                                                            Coef cf, double beta1, double beta2,
-                                                           uint16_t* __restrict__ pb) {
+                                                           uint16_t* __restrict__ pb,
+                                                           const float* __restrict__ clip) {
   __shared__ double red[8];
   __shared__ float bcs[2];
   const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
   if (t == 0) bias_corrections(rec->done + 1, beta1, beta2, bcs[0], bcs[1]);
   __syncthreads();
   const float bc1 = bcs[0], sbc2 = bcs[1];
+  const float coef = CLIP ? clip[kClipCoef] : 1.f;
   int c0, c1;
   chunk_range(tb, seg_lo, seg_hi, c0, c1);
   for (int c = c0 + (int)blockIdx.x; c < c1; c += (int)gridDim.x) {
@@ -97,6 +104,7 @@ __global__ void __launch_bounds__(256) lamb_moments_kernel(float* __restrict__ p
     const int lead = min(n, (int)((4 - (s & 3)) & 3));
     double sp = 0.0, su = 0.0;
     auto step = [&](float& pp, float gg, float& mm, float& vv) {
+      if (CLIP) gg = coef * gg;
       moments(gg, mm, vv, cf);
       const float u = direction(pp, mm, vv, wde, bc1, sbc2, cf.eps);
       if (!fin) {
@@ -153,7 +161,8 @@ __global__ void __launch_bounds__(256) lamb_moments_kernel(float* __restrict__ p
 // one wave per segment; lane 0 of block 0 alone touches the record
 __global__ void __launch_bounds__(64) lamb_trust_kernel(Table tb, const double* __restrict__ partials,
                                                         float* __restrict__ trust, LambRecord* __restrict__ rec,
-                                                        int seg_lo, double beta1, double beta2, bool advance) {
+                                                        int seg_lo, double beta1, double beta2, bool advance,
+                                                        bool trust_clip) {
   const int seg = seg_lo + (int)blockIdx.x;
   const int lane = threadIdx.x;
   if (blockIdx.x == 0 && lane == 0) {
@@ -180,6 +189,7 @@ __global__ void __launch_bounds__(64) lamb_trust_kernel(Table tb, const double* 
 #pragma clang fp contract(off)  // round every operation, as the float64 reference does
       tr = (float)(sqrt(sp) / sqrt(su));
     }
+    if (trust_clip && tr > 1.f) tr = 1.f;
   }
   if (lane == 0) trust[seg] = tr;
 }
@@ -269,8 +279,8 @@ static Coef coef_of(const LambHyper& h) {
   return c;
 }
 
-template <bool SINGLE>
-static void launch_moments_t(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,
+template <bool SINGLE, bool CLIP>
+static void launch_moments_c(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,
                              const LambHyper& h, hipStream_t st) {
   Table tb = table_of(sp, seg_lo, seg_hi);
   check_bufs(b, true);
@@ -278,11 +288,20 @@ static void launch_moments_t(const LambBufs& b, const LambSpace& sp, int seg_lo,
   dim3 gr(chunk_grid(sp, max_chunks)), bl(256);
   const Coef cf = coef_of(h);
   if (b.mirror)
-    hipLaunchKernelGGL((lamb_moments_kernel<SINGLE, true>), gr, bl, 0, st, b.p, b.g, b.m, b.v, tb, sp.rec,
-                       sp.partials, seg_lo, seg_hi, cf, h.beta1, h.beta2, b.mirror);
+    hipLaunchKernelGGL((lamb_moments_kernel<SINGLE, true, CLIP>), gr, bl, 0, st, b.p, b.g, b.m, b.v, tb, sp.rec,
+                       sp.partials, seg_lo, seg_hi, cf, h.beta1, h.beta2, b.mirror, b.clip);
   else
-    hipLaunchKernelGGL((lamb_moments_kernel<SINGLE, false>), gr, bl, 0, st, b.p, b.g, b.m, b.v, tb, sp.rec,
-                       sp.partials, seg_lo, seg_hi, cf, h.beta1, h.beta2, (uint16_t*)nullptr);
+    hipLaunchKernelGGL((lamb_moments_kernel<SINGLE, false, CLIP>), gr, bl, 0, st, b.p, b.g, b.m, b.v, tb, sp.rec,
+                       sp.partials, seg_lo, seg_hi, cf, h.beta1, h.beta2, (uint16_t*)nullptr, b.clip);
+}
+
+template <bool SINGLE>
+static void launch_moments_t(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,
+                             const LambHyper& h, hipStream_t st) {
+  if (b.clip)
+    launch_moments_c<SINGLE, true>(b, sp, seg_lo, seg_hi, max_chunks, h, st);
+  else
+    launch_moments_c<SINGLE, false>(b, sp, seg_lo, seg_hi, max_chunks, h, st);
 }
 
 void launch_lamb_moments(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,
@@ -297,7 +316,7 @@ void launch_lamb_trust(const LambSpace& sp, int seg_lo, int seg_hi, const LambHy
   Table tb = table_of(sp, seg_lo, seg_hi);
   if (!sp.partials || !sp.trust) throw std::runtime_error("lamb: missing partials / trust");
   hipLaunchKernelGGL(lamb_trust_kernel, dim3((unsigned)(seg_hi - seg_lo)), dim3(64), 0, st, tb, sp.partials,
-                     sp.trust, sp.rec, seg_lo, h.beta1, h.beta2, advance);
+                     sp.trust, sp.rec, seg_lo, h.beta1, h.beta2, advance, h.trust_clip);
 }
 
 void launch_lamb_update(const LambBufs& b, const LambSpace& sp, int seg_lo, int seg_hi, int max_chunks,

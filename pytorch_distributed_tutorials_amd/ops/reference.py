@@ -11,6 +11,7 @@ Layout conventions shared with the kernels (``csrc/kernels/*.hip``):
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -240,8 +241,18 @@ def lars_momentum_(params, grads, bufs, lr: float, momentum: float, dampening: f
         sgd_momentum_([p], [d], [b], lr, momentum, dampening, 0.0, nesterov, first_step)
 
 
+def clip_coef(grads, max_norm: float):
+    """``(norm, coef)`` of ``torch.nn.utils.clip_grad_norm_`` over a list of tensors, as Python floats
+    from float64 sums of squares: ``norm = sqrt(sum g^2)`` and ``coef = min(max_norm / (norm + 1e-6), 1)``.
+    A NaN norm gives a NaN coefficient and an infinite one 0, as torch's clamp does."""
+    norm = math.sqrt(sum(float(g.detach().double().pow(2).sum()) for g in grads))
+    c = max_norm / (norm + 1e-6)
+    return norm, (1.0 if c >= 1.0 else c)
+
+
 def lamb_(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999,
-          eps: float = 1e-6, weight_decay: float = 0.0, trust: bool = True, exclude_1d: bool = True):
+          eps: float = 1e-6, weight_decay: float = 0.0, trust: bool = True, exclude_1d: bool = True,
+          grad_coef: float = 1.0, trust_clip: bool = False):
     """LAMB (You et al. 2020) on lists of tensors, update number ``step = 1, 2, ...``; returns the
     trust ratio of every tensor.  Per tensor, with ``bc1 = 1 - beta1**step`` and
     ``bc2 = 1 - beta2**step`` in float64 (a float32 tensor rounds them, and ``sqrt(bc2)``, to float32)::
@@ -255,7 +266,8 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float, beta1: flo
 
     ``exclude_1d``: tensors with ``ndim <= 1`` get neither weight decay nor the ratio, as in
     ``lars_momentum_``.  ``trust=False`` is AdamW (with ``exclude_1d=False``, ``torch.optim.AdamW`` in
-    exact arithmetic).  No gradient-norm clipping and no clamp of the ratio."""
+    exact arithmetic).  ``grad_coef`` (``clip_coef``'s coefficient) multiplies every gradient first,
+    rounded to the tensors' dtype; ``trust_clip`` clamps the ratio at 1.  The gradients are not modified."""
     if step < 1:
         raise ValueError(f"lamb_: update numbers start at 1, got {step}")
     bc1 = 1.0 - beta1 ** step
@@ -263,6 +275,8 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float, beta1: flo
     ratios = []
     for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
         excluded = bool(exclude_1d and p.ndim <= 1)
+        if grad_coef != 1.0:
+            g = g * grad_coef
         m.mul_(beta1).add_(g, alpha=1 - beta1)
         v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
         u = (m / bc1) / (v.sqrt() / sbc2 + eps)
@@ -274,6 +288,8 @@ def lamb_(params, grads, exp_avgs, exp_avg_sqs, step: int, lr: float, beta1: flo
             un = float(u.double().pow(2).sum().sqrt())
             if pn != 0 and un != 0:
                 ratio = float(torch.tensor(pn / un, dtype=torch.float64).float())
+            if trust_clip and ratio > 1.0:
+                ratio = 1.0
         p.add_(u, alpha=-lr * ratio)
         ratios.append(ratio)
     return ratios

@@ -4,7 +4,18 @@
 plus decoupled weight decay, ``u = m_hat / (sqrt(v_hat) + eps) + wd * p``, scaled per parameter tensor
 by the trust ratio ``|p| / |u|``.  BatchNorm weights and biases and the fc bias (``exclude_1d``: every
 tensor with ``ndim <= 1``, exactly as ``LARS``) get neither weight decay nor the ratio.
-``trust=False`` is AdamW.  There is no gradient-norm clipping and no clamp of the ratio.
+``trust=False`` is AdamW.
+
+``max_grad_norm > 0`` clips the gradient by its global L2 norm before the moments, with
+``torch.nn.utils.clip_grad_norm_``'s coefficient ``min(max_grad_norm / (norm + 1e-6), 1)`` (timm's
+``Lamb(max_grad_norm=1.0)`` is the optimizer of the "ResNet strikes back" recipe); ``trust_clip`` clamps
+the ratio at 1.  On the flat path the norm is two launches over the flat gradient buffer
+(``csrc/opt/clip.hip``: float64 sums over fixed 4096-element chunks, a one-block finalize) that leave
+``(norm, coef)`` in a device record; the first LAMB / AdamW pass reads the record and multiplies each
+gradient element as it loads it, so a clipped step pays one extra 4 B per parameter read and no scale
+pass, and the host never sees the norm.  ``grad_flat`` itself is left unscaled on this path: nothing
+reads it after the step.  The norm is taken over the flat space (the per-tensor path: over every
+gradient of the optimizer).  Neither setting is part of ``state_dict()``: a resumed run passes them again.
 
 When a param group is exactly the set of parameters of a ``FlatParamSpace`` on the GPU, the step is
 three streaming launches over the flat param / grad / moment buffers (``csrc/opt/lamb.hip``; one
@@ -19,12 +30,14 @@ ratios from its copy of the all-reduced gradients.
 """
 from __future__ import annotations
 
+import math
 from types import SimpleNamespace
 
 import torch
 
 from ..ops import reference as ref
 from ..ops._ext import native_opt
+from .clip import clip_buffers
 from .lars import LarsTable
 from .sgd import SGD
 
@@ -38,7 +51,8 @@ class LAMB(torch.optim.Optimizer):
     """
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
-                 weight_decay: float = 0.0, trust: bool = True, exclude_1d: bool = True):
+                 weight_decay: float = 0.0, trust: bool = True, exclude_1d: bool = True,
+                 max_grad_norm: float = 0.0, trust_clip: bool = False):
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
@@ -47,6 +61,10 @@ class LAMB(torch.optim.Optimizer):
             raise ValueError(f"Invalid eps: {eps}")
         if weight_decay < 0.0:
             raise ValueError(f"Invalid weight_decay: {weight_decay}")
+        if not (math.isfinite(max_grad_norm) and max_grad_norm >= 0.0):
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        # kept off the param groups: state_dict() stays torch.optim.Adam's
+        self.max_grad_norm, self.trust_clip = float(max_grad_norm), bool(trust_clip)
         defaults = dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
                         trust=bool(trust), exclude_1d=bool(exclude_1d))
         super().__init__(params, defaults)
@@ -73,7 +91,11 @@ class LAMB(torch.optim.Optimizer):
                 v=old.v if old else torch.zeros_like(sp.param_flat),
                 # the device record: [0] = finished updates, [1] = the bias corrections in flight
                 rec=old.rec if old else torch.zeros(int(native_opt().record_elems()), dtype=torch.int64,
-                                                    device=sp.param_flat.device))
+                                                    device=sp.param_flat.device),
+                # the clipping's float64 partials and its device record (norm, coef)
+                gpart=old.gpart if old else None, clip=old.clip if old else None)
+            if fs.clip is None and self.max_grad_norm > 0.0:
+                fs.gpart, fs.clip = clip_buffers(sp.numel, sp.param_flat.device)
             self._flat[id(sp)] = fs
             for p, o in zip(sp.params, sp.offsets):
                 st = self.state[p]
@@ -88,6 +110,7 @@ class LAMB(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        coef = None  # the per-tensor path's coefficient: one global norm, taken when first needed
         for group in self.param_groups:
             (b1, b2), lr, eps, wd = group["betas"], group["lr"], group["eps"], group["weight_decay"]
             sp = self._flat_space_of(group)
@@ -97,12 +120,21 @@ class LAMB(torch.optim.Optimizer):
                 fs = self._flat_state(sp, group["exclude_1d"])
                 mirror = sp.mirror()
                 tb = fs.table
-                native_opt().lamb_step(sp.param_flat, sp.grad_flat, fs.m, fs.v, tb.table, tb.partials, tb.trust,
-                                       fs.rec, 0, tb.nseg, lr, b1, b2, eps, wd, group["trust"], True,
-                                       mirror.krsc if mirror is not None else None)
+                krsc = mirror.krsc if mirror is not None else None
+                if fs.clip is None and not self.trust_clip:  # exactly the calls of a step without clipping
+                    native_opt().lamb_step(sp.param_flat, sp.grad_flat, fs.m, fs.v, tb.table, tb.partials, tb.trust,
+                                           fs.rec, 0, tb.nseg, lr, b1, b2, eps, wd, group["trust"], True, krsc)
+                else:
+                    if fs.clip is not None:
+                        native_opt().grad_norm(sp.grad_flat, fs.gpart, fs.clip, self.max_grad_norm)
+                    native_opt().lamb_step(sp.param_flat, sp.grad_flat, fs.m, fs.v, tb.table, tb.partials, tb.trust,
+                                           fs.rec, 0, tb.nseg, lr, b1, b2, eps, wd, group["trust"], True, krsc,
+                                           clip=fs.clip, trust_clip=self.trust_clip)
                 if mirror is not None:
                     mirror.after_optimizer_step()  # bf16 conv weights for the next forward
                 continue
+            if coef is None:
+                coef = ref.clip_coef(self._loose_grads(), self.max_grad_norm)[1] if self.max_grad_norm > 0.0 else 1.0
             for p in group["params"]:
                 if p.grad is None:
                     continue
@@ -113,8 +145,17 @@ class LAMB(torch.optim.Optimizer):
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
                 ref.lamb_([p], [p.grad], [st["exp_avg"]], [st["exp_avg_sq"]], int(st["step"]), lr, b1, b2, eps, wd,
-                          group["trust"], group["exclude_1d"])
+                          group["trust"], group["exclude_1d"], coef, self.trust_clip)
         return loss
+
+    def _loose_grads(self):
+        """The gradients of every group that takes the per-tensor path."""
+        out = []
+        for group in self.param_groups:
+            sp = self._flat_space_of(group)
+            if sp is None or not sp.param_flat.is_cuda:
+                out += [p.grad for p in group["params"] if p.grad is not None]
+        return out
 
     def _flat_groups(self):
         for group in self.param_groups:

@@ -19,6 +19,7 @@ stdout lines of ``resnet/main.py:107,113-115``.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 from typing import Optional
@@ -30,7 +31,7 @@ from . import ops
 from .data import (AugConfig, CenterCropResize, DeviceLoader, DistributedSampler, MixConfig, RandomResizedCrop,
                    build_dataset)
 from .models import build_model
-from .optim import LAMB, LARS, SGD, ModelEma, WarmupCosineLR, WarmupPolyLR
+from .optim import LAMB, LARS, SGD, ModelEma, WarmupCosineLR, WarmupPolyLR, clip_grad_norm_
 from .parallel import DistributedDataParallel, destroy, init_distributed
 from .parallel.comm import CommOptions
 from .utils.checkpoint import load_checkpoint, save_checkpoint
@@ -117,6 +118,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--lamb-adapt-1d", action="store_true",
                    help="LAMB / AdamW: also decay (and, for LAMB, adapt) BatchNorm parameters and biases "
                         "(exclude_1d off)")
+    p.add_argument("--clip-grad-norm", type=float, default=0.0, metavar="V",
+                   help="clip the gradient by its global L2 norm to V before the update, on the device "
+                        "(optim.clip_grad_norm_; lamb / adamw read the coefficient inside their first pass); "
+                        "sgd / lars then update after backward, not per bucket inside it; 0 = off")
+    p.add_argument("--lamb-trust-clip", action="store_true", help="LAMB: clamp the trust ratios at 1")
     p.add_argument("--label-smoothing", type=float, default=0.0)
     p.add_argument("--loss", default="ce", choices=["ce", "bce"],
                    help="bce: binary cross entropy, every class an independent sigmoid, against the smoothed "
@@ -200,8 +206,9 @@ class _GraphStep:
 
     WARMUP = 3
 
-    def __init__(self, ddp_model, criterion, optimizer, period: int = 1):
+    def __init__(self, ddp_model, criterion, optimizer, period: int = 1, clip_grad_norm: float = 0.0):
         self.ddp_model, self.criterion, self.optimizer = ddp_model, criterion, optimizer
+        self.clip_grad_norm = clip_grad_norm  # > 0: clip between backward and step(), on the device
         self.period = period  # 3 with fp8: the delayed-scaling slot ring (utils.graph.CapturedStep)
         self.x = self.y = None
         self.warm = 0
@@ -218,6 +225,8 @@ class _GraphStep:
         self.optimizer.zero_grad()
         loss = self.criterion(self.ddp_model(inputs), labels)
         loss.backward()
+        if self.clip_grad_norm > 0.0:
+            clip_grad_norm_(self.ddp_model.space, self.clip_grad_norm)
         self.optimizer.step()
         return loss
 
@@ -280,6 +289,10 @@ def main(argv: Optional[list] = None) -> int:
         raise SystemExit(f"--beta1 / --beta2 must be in [0, 1), got {args.beta1}, {args.beta2}")
     if args.adam_eps < 0.0:
         raise SystemExit(f"--adam-eps must be >= 0, got {args.adam_eps}")
+    if not (math.isfinite(args.clip_grad_norm) and args.clip_grad_norm >= 0.0):
+        raise SystemExit(f"--clip-grad-norm must be finite and >= 0 (0 = off), got {args.clip_grad_norm}")
+    if args.lamb_trust_clip and args.optimizer != "lamb":
+        raise SystemExit(f"--lamb-trust-clip needs --optimizer lamb, got --optimizer {args.optimizer}")
     try:
         mix = MixConfig(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.mix_switch_prob).validate()
     except ValueError as e:
@@ -380,20 +393,24 @@ def main(argv: Optional[list] = None) -> int:
         ddp_model.enable_comm_timing(True)
     inject = FaultInjector(env.rank)
     # a captured step keeps the post-backward update (the per-bucket one's local-mode reducer made
-    # graph replay ~2.7x slower, bench.py --graph)
+    # graph replay ~2.7x slower, bench.py --graph), and so does a clipped one: a per-bucket update
+    # inside backward cannot know the global norm
+    overlap = False if args.graph or args.clip_grad_norm > 0.0 else None
+    # sgd / lars cannot read the clip record: their gradient is scaled in place before step()
+    step_clip = args.clip_grad_norm if args.optimizer in ("sgd", "lars") else 0.0
     if args.optimizer == "lars":
         optimizer = LARS(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
                          weight_decay=args.weight_decay, trust_coefficient=args.trust_coefficient,
-                         eps=args.lars_eps, exclude_1d=not args.lars_adapt_1d,
-                         overlap=False if args.graph else None)
+                         eps=args.lars_eps, exclude_1d=not args.lars_adapt_1d, overlap=overlap)
     elif args.optimizer in ("lamb", "adamw"):
         # always the post-backward step (optim/lamb.py): nothing to attach, with or without --graph
         optimizer = LAMB(ddp_model.parameters(), lr=args.learning_rate, betas=(args.beta1, args.beta2),
                          eps=args.adam_eps, weight_decay=args.weight_decay, trust=args.optimizer == "lamb",
-                         exclude_1d=not args.lamb_adapt_1d)
+                         exclude_1d=not args.lamb_adapt_1d, max_grad_norm=args.clip_grad_norm,
+                         trust_clip=args.lamb_trust_clip)
     else:
         optimizer = SGD(ddp_model.parameters(), lr=args.learning_rate, momentum=args.momentum,
-                        weight_decay=args.weight_decay, overlap=False if args.graph else None)
+                        weight_decay=args.weight_decay, overlap=overlap)
 
     # every rank keeps its own, identical EMA (the parameters are the same everywhere): no collectives
     ema = ModelEma(ddp_model, args.ema_decay, every=args.ema_every, warmup=args.ema_warmup) \
@@ -424,8 +441,8 @@ def main(argv: Optional[list] = None) -> int:
                                 device=device, seed=args.seed + env.rank, mix=mix, transform=train_tf, aug=aug)
     test_loader = DeviceLoader(test_set, 128, shuffle=False, augment=False, device=device, transform=eval_tf)
 
-    graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1) \
-        if args.graph else None
+    graph_step = _GraphStep(ddp_model, criterion, optimizer, period=3 if dtype == "fp8" else 1,
+                            clip_grad_norm=step_clip) if args.graph else None
     steps_per_epoch = len(train_loader)
     if args.max_steps_per_epoch is not None:
         steps_per_epoch = min(steps_per_epoch, args.max_steps_per_epoch)
@@ -498,6 +515,8 @@ def main(argv: Optional[list] = None) -> int:
                 with trace.trace_range("backward"):
                     loss.backward()
                 with trace.trace_range("optimizer"):
+                    if step_clip > 0.0:
+                        clip_grad_norm_(ddp_model.space, step_clip)
                     optimizer.step()
             if ema is not None:  # eager also under --graph: warm-up and --ema-every stay host-side
                 ema.update()

@@ -18,11 +18,18 @@ Isolated, on the model's real flat parameter space (``n`` parameters, ``x`` of t
 * ``sgd_step``      ``_C.sgd_step`` with momentum and the mirror on a space of the same size, 22 B per
                     parameter.  The yardstick: the same streaming pattern;
 * ``torch_adamw``   ``torch.optim.AdamW(foreach=True)`` on the stock module's 161 tensors: what the kernels
-                    replace (28 B per parameter counted, no bf16 image).
+                    replace (28 B per parameter counted, no bf16 image);
+* ``grad_norm``     the clipping's two launches (``_C_opt.grad_norm``): the gradient read once, 4 B per parameter;
+* ``lamb_clip`` / ``adamw_clip``  ``grad_norm`` and then the step with ``clip=``: the bytes of the step plus 4 B
+                    per parameter (the first pass multiplies as it loads; there is no scale pass);
+* ``scale_clipped`` / ``scale_unclipped``  ``_C_opt.scale_grads`` with a coefficient below 1 (g read and
+                    written, 8 B per parameter) and of exactly 1 (every block returns: the launch alone).
 
 In the step (``--skip-step`` leaves it out): the ``bench.py`` training step (native model behind the DDP
 wrapper, batch x 3 x size x size synthetic input) with ``optim.SGD`` (momentum 0.9, per-bucket update),
-``optim.LAMB`` and ``optim.LAMB(trust=False)``; ms per step over ``--step-iters`` back-to-back steps.
+``optim.LAMB`` and ``optim.LAMB(trust=False)``, and each of the three with gradient-norm clipping at 1.0
+(``max_grad_norm=`` for LAMB / AdamW; for SGD ``overlap=False`` and ``optim.clip_grad_norm_`` between backward
+and ``step()``); ms per step over ``--step-iters`` back-to-back steps.
 
 Method of ``scripts/bench_ema.py``: one process, device events, a warm-up, the candidates alternating
 round by round, the figure per candidate the median round with min-max.  Bytes are counted from the
@@ -61,7 +68,8 @@ def main(argv=None) -> int:
     from pytorch_distributed_tutorials_amd import ops
     from pytorch_distributed_tutorials_amd.models import build_model
     from pytorch_distributed_tutorials_amd.ops._ext import native, native_opt
-    from pytorch_distributed_tutorials_amd.optim import LAMB, SGD
+    from pytorch_distributed_tutorials_amd.optim import LAMB, SGD, clip_grad_norm_
+    from pytorch_distributed_tutorials_amd.optim.clip import clip_buffers
     from pytorch_distributed_tutorials_amd.parallel import DistributedDataParallel
 
     C, O = native(), native_opt()
@@ -96,6 +104,14 @@ def main(argv=None) -> int:
         q.grad = torch.randn_like(q) * 1e-2
     tadamw = torch.optim.AdamW(stock.parameters(), lr=1e-4, eps=1e-6, weight_decay=0.01, foreach=True)
 
+    gpart, clip = clip_buffers(n, dev)
+    g3 = g2.clone()  # scaled in place, 0.9999 x per call
+    below, one = torch.tensor([1.0, 0.9999], device=dev), torch.ones(2, device=dev)
+
+    def clipped(use_trust):
+        O.grad_norm(g2, gpart, clip, 1.0)
+        O.lamb_step(p2, g2, m2, v2, *common, use_trust, True, k2, clip=clip)
+
     cands = {
         "adamw": lambda: O.lamb_step(p2, g2, m2, v2, *common, False, True, k2),
         "lamb": lambda: O.lamb_step(p2, g2, m2, v2, *common, True, True, k2),
@@ -104,10 +120,17 @@ def main(argv=None) -> int:
         "lamb_update": lambda: O.lamb_update(p2, m2, v2, *common, k2),
         "sgd_step": lambda: C.sgd_step(p2, g2, b2, 1e-4, 0.9, 0.0, 1e-5, False, False, 1.0, k2),
         "torch_adamw": tadamw.step,
+        "grad_norm": lambda: O.grad_norm(g2, gpart, clip, 1.0),
+        "lamb_clip": lambda: clipped(True),
+        "adamw_clip": lambda: clipped(False),
+        "scale_clipped": lambda: O.scale_grads(g3, below),
+        "scale_unclipped": lambda: O.scale_grads(g3, one),
     }
     pass1 = 24 * n_adapt + 30 * n_excl
     nbytes = {"adamw": 30 * n, "lamb": pass1 + 18 * n_adapt, "lamb_moments": pass1, "lamb_trust": pass1,
-              "lamb_update": 18 * n_adapt, "sgd_step": 22 * n, "torch_adamw": 28 * n}
+              "lamb_update": 18 * n_adapt, "sgd_step": 22 * n, "torch_adamw": 28 * n, "grad_norm": 4 * n,
+              "lamb_clip": pass1 + 18 * n_adapt + 4 * n, "adamw_clip": 34 * n, "scale_clipped": 8 * n,
+              "scale_unclipped": 0}
 
     def timed(fn, iters):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -137,27 +160,38 @@ def main(argv=None) -> int:
         "adamw_over_sgd_GBps": round(gbps["adamw"] / gbps["sgd_step"], 3),
         "lamb_over_sgd_GBps": round(gbps["lamb"] / gbps["sgd_step"], 3),
         "torch_adamw_over_adamw_us": round(us["torch_adamw"] / us["adamw"], 1),
+        "grad_norm_over_sgd_GBps": round(gbps["grad_norm"] / gbps["sgd_step"], 3),
+        "lamb_clip_minus_lamb_us": round(us["lamb_clip"] - us["lamb"], 2),
+        "adamw_clip_minus_adamw_us": round(us["adamw_clip"] - us["adamw"], 2),
+        "clip_coef": round(float(clip[1].item()), 6),
     }
 
     if not a.skip_step:
-        del p2, g2, m2, v2, b2, k2, tadamw, stock
+        del p2, g2, g3, m2, v2, b2, k2, tadamw, stock
         torch.cuda.empty_cache()
         g = torch.Generator(device="cpu").manual_seed(1234)
         images = torch.randn((a.batch, 3, a.size, a.size), generator=g).to(dev)
         labels = torch.randint(0, a.num_classes, (a.batch,), generator=g).to(dev)
         criterion = ops.CrossEntropyLoss()
 
-        def stepper(ddp, opt):
+        def stepper(ddp, opt, clip_to=0.0):
             def step():
                 opt.zero_grad()
                 loss = criterion(ddp(images), labels)
                 loss.backward()
+                if clip_to > 0.0:
+                    clip_grad_norm_(ddp.space, clip_to)
                 opt.step()
             return step
 
         cfgs = {"lamb": stepper(ddp, lamb),
                 "sgd": stepper(*build(lambda ps: SGD(ps, lr=0.01, momentum=0.9, weight_decay=1e-5))),
-                "adamw": stepper(*build(lambda ps: LAMB(ps, lr=1e-4, weight_decay=0.01, trust=False)))}
+                "adamw": stepper(*build(lambda ps: LAMB(ps, lr=1e-4, weight_decay=0.01, trust=False))),
+                "lamb_clip": stepper(*build(lambda ps: LAMB(ps, lr=1e-4, weight_decay=0.01, max_grad_norm=1.0))),
+                "adamw_clip": stepper(*build(lambda ps: LAMB(ps, lr=1e-4, weight_decay=0.01, trust=False,
+                                                             max_grad_norm=1.0))),
+                "sgd_clip": stepper(*build(lambda ps: SGD(ps, lr=0.01, momentum=0.9, weight_decay=1e-5,
+                                                          overlap=False)), clip_to=1.0)}
         for run in cfgs.values():
             timed(run, 8)
         srounds = {k: [] for k in cfgs}
